@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- aligned Gbases/s of the seed-chain-extend hot path on MI355X (BASELINE.json: map-ont, ~10 kb reads, -a).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--ref-mb 3000] [--reads 100000] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--ref-mb 3000] [--reads 100000] [--scaling strong|weak] [--full] [--dump-outputs DIR]
 
 One "step" = one mini-batch of --reads synthetic ONT-like reads through the reference's three pipeline steps (map.c:541-643) as this library
 replaces them: hand-over of the reads' host buffers (mm_gpu_batch_stage_queued: pinned-memory packing + H2D, run beside the mapping
@@ -15,9 +15,16 @@ torch.distributed.run): every rank builds the same index replica; with --scaling
 (minimap2_amd/shard.py: split_by_bases); with --scaling weak every rank maps a batch of --reads of its own.  The packed hit
 records are gathered to rank 0 over RCCL inside the timed region (pinned buffers), and every rank formats the SAM text of its own shard.
 
-Rank 0 prints ONE JSON line.  "roofline" is the dominant kernel's algorithmic bytes / its HIP-event time on the launch
-stream; "cpu_baseline" is the UNMODIFIED reference's mm_map on all host cores over a bounded sample of the same batch
-against the same index contents (oracle/_ref; N=1 only)."""
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, warms up, times the --steps steps, writes
+the outputs of the last one (--dump-outputs) and prints the line.  --full adds everything else after the clock: the parity checks of the
+timed path's text (pipeline_text_identical; N > 1: text_identical_to_n1), the side figures (resident, hand-over then map, the output
+stage alone), "roofline" -- the dominant kernel's algorithmic bytes / its HIP-event time on the launch stream (the per-kernel events are
+recorded in the timed steps of a --full run only) and the one-lane pass behind roofline.valu -- and "cpu_baseline", the UNMODIFIED
+reference's mm_map on all host cores over a bounded sample of the same batch against the same index contents (oracle/_ref; N=1 only).
+In a plain run these entries are null.
+
+--dump-outputs DIR: after the clock, the SAM records the timed path produced for its last step, one float64 array per field as
+DIR/<field>.npy (dump_outputs below).  The inputs are seeded, so two builds run with the same arguments can be compared record for record."""
 import argparse
 import math
 import ctypes as C
@@ -268,6 +275,62 @@ def gen_pairs(torch, dev, seed, codes, per, n_contig, n_pairs, read_len, err):
     return out[0], out[1]
 
 
+DUMP_TAGS = ("NM", "ms", "AS", "nn", "tp", "cm", "s1", "s2", "de", "rl")  # the numeric (and tp:A) tags of the SAM writer (format.c)
+DUMP_MAX_READS = 100000      # reads whose records are written: all of them up to this, beyond it a fixed, seeded sample
+DUMP_MAX_RECORDS = 300000    # x (10 fields + the tags + 1 digest) x 8 bytes: at most 50 MB in all
+
+
+def dump_outputs(path, addr, ln, n_reads, names):
+    """--dump-outputs: the SAM text the timed path produced for its last step (the output stage's reused buffer at `addr`, `ln` bytes),
+    one float64 array per field as path/<field>.npy, one entry per record: read (the index in the read's name), flag, rid (RNAME's
+    contig index, -1 for *), pos, mapq, cigar (a 48-bit digest of the CIGAR string), rnext (-1 for *, -2 for =), pnext, tlen, seq_len,
+    tag_<XX> for each of DUMP_TAGS (tp:A as its character code; NaN where absent) and record (a 48-bit digest of the whole line).
+    Records are ordered by read and keep their order within a read, so the dump does not depend on the batch's rotation.  Beyond
+    DUMP_MAX_READS reads, only a seeded sample of read indices is kept; beyond DUMP_MAX_RECORDS records, only the first ones in that
+    order.  (N > 1: rank 0's shard.)  Returns the number of records written."""
+    import hashlib
+
+    def digest(b):
+        return float(int.from_bytes(hashlib.blake2b(b, digest_size=6).digest(), "little"))  # < 2**48: exact in float64
+
+    keep = None
+    if n_reads > DUMP_MAX_READS:
+        keep = np.zeros(n_reads, dtype=bool)
+        keep[np.random.default_rng(20240601).choice(n_reads, DUMP_MAX_READS, replace=False)] = True
+    contig = {n.encode(): i for i, n in enumerate(names)}
+    view = np.ctypeslib.as_array((C.c_ubyte * ln).from_address(addr)) if ln else np.zeros(0, dtype=np.uint8)
+    chunk = 1 << 28
+    ends = [np.flatnonzero(view[o:o + chunk] == 10) + o for o in range(0, ln, chunk)]
+    ends = np.concatenate(ends) if ends else np.zeros(0, dtype=np.int64)
+    if ln and view[ln - 1] != 10:
+        ends = np.append(ends, ln)
+    cols = ["read", "flag", "rid", "pos", "mapq", "cigar", "rnext", "pnext", "tlen", "seq_len"] + ["tag_" + t for t in DUMP_TAGS] + ["record"]
+    tag_col = {t.encode(): 10 + i for i, t in enumerate(DUMP_TAGS)}
+    rows, s0 = [], 0
+    for e in ends.tolist():
+        line, s0 = view[s0:e].tobytes(), e + 1
+        if not line or line[:1] == b"@":
+            continue
+        f = line.split(b"\t")
+        ri = int(f[0][4:]) if f[0].startswith(b"read") else -1
+        if keep is not None and not (0 <= ri < n_reads and keep[ri]):
+            continue
+        r = [float(ri), float(f[1]), float(contig.get(f[2], -1)), float(f[3]), float(f[4]), digest(f[5]),
+             -1.0 if f[6] == b"*" else -2.0 if f[6] == b"=" else float(contig.get(f[6], -3)), float(f[7]), float(f[8]),
+             float(len(f[9]) if f[9] != b"*" else 0)] + [math.nan] * len(DUMP_TAGS) + [digest(line)]
+        for t in f[11:]:
+            c = tag_col.get(t[:2])
+            if c is not None:
+                r[c] = float(t[5:]) if t[3:4] in (b"i", b"f") else float(t[5]) if t[3:4] == b"A" else math.nan
+        rows.append(r)
+    tab = np.array(rows, dtype=np.float64).reshape(-1, len(cols))
+    tab = tab[np.argsort(tab[:, 0], kind="stable")][:DUMP_MAX_RECORDS]
+    os.makedirs(path, exist_ok=True)
+    for j, c in enumerate(cols):
+        np.save(os.path.join(path, c + ".npy"), np.ascontiguousarray(tab[:, j]))
+    return tab.shape[0]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -290,7 +353,12 @@ def main():
     ap.add_argument("--workload", default="plain", choices=["plain", "repeats"], help="plain: BASELINE.json's i.i.d. reference (the headline); repeats: a tenth of the reference is planted repeat families "
                     "(interspersed, segmental duplications, tandem arrays) and 5 %% of the reads carry a deletion / insertion / inversion -- a side figure: how much of the batch leaves the device path")
     ap.add_argument("--timed-only", action="store_true", help="profiling runs: nothing after the timed steps (no resident / one-lane / formatting / CPU passes), so that the end of a kernel trace IS the timed pipeline")
+    ap.add_argument("--full", action="store_true", help="also the parity checks, side figures, roofline and CPU baseline after the clock (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the SAM records of the last timed step as DIR/<field>.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras = a.full and not a.timed_only  # what runs after the clock besides the headline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -368,7 +436,7 @@ def main():
     if strong:  # this rank's share: contiguous, balanced by bases (pairs stay together: both mates in one entry)
         cut = shard.split_by_bases([len(r) + (len(mates[i]) if pairs else 0) for i, r in enumerate(reads)], world)
         first_read = cut[rank]
-        if rank == 0 and not a.timed_only:  # the whole batch, for the check that the N ranks' output IS the N = 1 output (after the clock)
+        if rank == 0 and extras:  # the whole batch, for the check that the N ranks' output IS the N = 1 output (after the clock)
             whole_named = [("read%d" % i, s, mates[i]) for i, s in enumerate(reads)] if pairs else [("read%d" % i, s) for i, s in enumerate(reads)]
         reads = reads[cut[rank]:cut[rank + 1]]
         if pairs:
@@ -426,7 +494,7 @@ def main():
     if a.warmup > 0:
         dt = run_steps(range(a.warmup))
         log("rank %d warmup (%d steps): %.3f s  stats=%s" % (rank, a.warmup, dt, {k: round(v, 3) for k, v in al.last_stats().items()}))
-    mm.profile_enable(not os.environ.get("MM2AMD_BENCH_NO_PROFILE"))  # (experiments: the timed steps without the per-kernel HIP events; the line then has no roofline)
+    mm.profile_enable(a.full and not os.environ.get("MM2AMD_BENCH_NO_PROFILE"))  # (--full: per-kernel HIP events for the roofline; MM2AMD_BENCH_NO_PROFILE: a --full line without it)
     import resource
 
     def thread_cpu():
@@ -459,6 +527,10 @@ def main():
     # (threads that ended inside the window -- the lane drivers of every batch, the pipeline's three -- are not in tc1: their share is the remainder)
     cpu_by_thread = {k: round((v - tc0.get(k, 0.0)) / max(a.steps, 1), 3) for k, v in sorted(tc1.items()) if v - tc0.get(k, 0.0) >= 0.005 * max(a.steps, 1)}
     sam_bytes_per_step = step_done[-1][1] if step_done else 0
+    if a.dump_outputs and last_text and rank == 0:  # before anything else formats: the text buffer is reused
+        t0 = time.time()
+        n_dumped = dump_outputs(a.dump_outputs, last_text[0][1], last_text[0][2], a.reads if strong else len(named), names)
+        log("outputs of the last timed step: %d SAM records written to %s in %.1f s" % (n_dumped, a.dump_outputs, time.time() - t0))
     # Parity of the timed path itself: the SAM text the pipeline produced for the LAST TIMED step -- still in the library's
     # reused buffer; hashed here, after the clock has stopped -- against the text of the same batch mapped outside the pipeline (mm_gpu_batch_stage +
     # mm_gpu_map_staged + mm_gpu_format_batch, the path the -m gpu suite pins to the compiled reference).
@@ -470,7 +542,7 @@ def main():
         return h.hexdigest()
     pipeline_text_identical = None
     step_text_lengths = sorted({ln for _, ln in step_done})
-    if last_text and world == 1 and not a.timed_only:
+    if last_text and world == 1 and extras:
         b_last, addr, ln = last_text[0]
         h_pipe = text_hash(addr, ln)
         al.stage(b_last)
@@ -488,7 +560,7 @@ def main():
     # (digests and lengths travel, not the text) and (b) the text it formats from the GATHERED hit records with its own.
     text_identical_to_n1 = None
     n1_check = None
-    if strong and not a.timed_only:
+    if strong and extras:
         ver = {}
         def on_mapped_v(b, n_reg, reg, rep_len):
             parts = shard.gather_payloads(shard.pack_hits(L, n_reg, reg, gbuf, tail=rep_len), dst=0, device=comm_dev, bufs=gbuf)
@@ -541,7 +613,7 @@ def main():
     drv_cpu_last_batch = {k: round(v, 3) for k, v in al.last_stats().items() if k.startswith("drv_cpu_")}  # the lane drivers' own CPU seconds per stage, last timed batch
     host_cpu_s = (ru1.ru_utime - ru0.ru_utime + ru1.ru_stime - ru0.ru_stime) / max(a.steps, 1)
     log("rank %d: host CPU time per step %.2f core-seconds (%d threads; hand-over, host stages of the mapping, hit gather, formatting)" % (rank, host_cpu_s, n_threads))
-    prof = {k: v for k, v in mm.profile_get().items() if v["launches"] > 0}  # (entries without launches are counts that go with a kernel: see extra1 below)
+    prof = {k: v for k, v in mm.profile_get().items() if v["launches"] > 0} if a.full else {}  # (entries without launches are counts that go with a kernel: see extra1 below)
     mm.profile_enable(False)
 
     def one_step(step, staged_outside=True):
@@ -560,7 +632,7 @@ def main():
     # side figures (rank 0, N = 1): the mapping call alone with the batch already resident (rounds 1-2's headline), and hand-over + mapping
     # one after the other (no pipeline)
     resident = pcie = None
-    if world == 1 and not a.timed_only:
+    if world == 1 and extras:
         resident = min(one_step(a.warmup + a.steps + i) for i in range(2))
         pcie = one_step(a.warmup + a.steps + 2, staged_outside=False)
     # un-overlapped kernel times: one more pass over the same batch with ONE lane (sub-batches one after the other, so no two
@@ -569,7 +641,7 @@ def main():
     extra1 = {}
     t_one = None
     stage_cpu = None
-    if rank == 0 and world == 1 and not a.timed_only:
+    if rank == 0 and world == 1 and extras:
         os.environ["MM2AMD_ACTIVE_LANES"] = "1"
         os.environ["MM2AMD_NO_SIDE_STREAM"] = "1"  # the lane-exact DP launches after the gap-fill kernel instead of beside it
         mm.profile_enable(True)
@@ -582,7 +654,7 @@ def main():
         mm.profile_enable(False)
         del os.environ["MM2AMD_ACTIVE_LANES"], os.environ["MM2AMD_NO_SIDE_STREAM"]
     fmt = None
-    if world == 1 and not a.timed_only:  # the output stage on its own (it runs beside the mapping in the timed region)
+    if world == 1 and extras:  # the output stage on its own (it runs beside the mapping in the timed region)
         try:
             b = base
             al.stage(b)
@@ -761,7 +833,7 @@ def main():
                 pass
 
     cpu = None
-    if world == 1 and not a.no_cpu_baseline and not a.timed_only:
+    if world == 1 and not a.no_cpu_baseline and extras:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import reflib

@@ -123,7 +123,7 @@ def test_bench_n_ranks_produce_the_n1_text(world):
     s.close()
     env = dict(os.environ, MM2AMD_BENCH_BACKEND="gloo", MM2AMD_EMU="1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--ref-mb", "1", "--reads", "25", "--read-len", "3000", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--ref-mb", "1", "--reads", "25", "--read-len", "3000", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900, cwd="/tmp")
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = json.loads(p.stdout.decode().strip().split("\n")[-1])

@@ -34,7 +34,7 @@ def collect(counter, args):
     subprocess.run(["rm", "-rf", out])
     env = dict(os.environ, MM2AMD_LANES="1", TMPDIR="/tmp", MM2AMD_DEVICE_FINISH="1")  # (region_finish_kernel on, so that it is counted too)
     cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "-d", out, "-o", "pmc", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-           "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--reads", str(args.reads), "--ref-mb", str(args.ref_mb), "--preset", args.preset]
+           "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--reads", str(args.reads), "--ref-mb", str(args.ref_mb), "--preset", args.preset]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True)
     try:  # the bench line of the same run: algorithmic bytes and launches per launch class, as the launches account them
         line = json.loads(p.stdout.decode().strip().split("\n")[-1])
