@@ -34,6 +34,7 @@ struct SeedChainParams {          // what mm_map_frag_core passes to seeding and
 	// 1: the caller takes the chains through align_regions(): seed_chain() leaves the chained anchors and the minimizer positions on the device
 	// (ReadChains::a_p / mp_p null, the counts set); fetch_chains() brings the reads the host has to see
 	int lazy_chains = 0;
+	int chain_dump = 1;           // 0: this call writes no MM2AMD_CHAIN_DUMP blocks (the second seeding of map.c:293-316, whose chains replace the first ones)
 	int long_join = 0, bw_long = 0, rmq_rescue_size = 0;
 	float rmq_rescue_ratio = 0;
 };

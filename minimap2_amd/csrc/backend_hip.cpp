@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <thread>
 #include "backend.hpp"
+#include "chain_dump.hpp"
 #include "chain_host.hpp"
 #include "device_ctx.hpp"
 #include "ksw_host.hpp"
@@ -218,7 +219,7 @@ public:
 		}
 		HIP_CHECK(hipMemcpyAsync(d_seq_off_.p, seq_off_.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream_));
 		read_names_.clear();
-		if (getenv("MM2AMD_SEED_DUMP")) for (size_t i = 0; i < n; ++i) read_names_.push_back(reads[i].name);
+		if (getenv("MM2AMD_SEED_DUMP") || chain_dump_path()) for (size_t i = 0; i < n; ++i) read_names_.push_back(reads[i].name);
 		have_read_names_ = false;
 		if (name_rules_ && n > 0) { // strcmp(qname, target name) as two ranks per read (see skip_hit in seed_chain.hip)
 			have_read_names_ = true;
@@ -381,6 +382,13 @@ public:
 				fclose(fp);
 			}
 		}
+		const char *cdump = P.chain_dump ? chain_dump_path() : nullptr; // diagnostics: every read's chains (chain_dump.hpp)
+		auto dump_block = [&](size_t i) { // what every block of read i of this call says about the read
+			ChainDumpBlock b;
+			b.name = read_names_.empty() ? nullptr : read_names_[lo + i];
+			b.qlen = (int)(seq_off_[lo + i + 1] - seq_off_[lo + i]), b.n_seg = has_pairs_ ? unit_first_[lo + i + 1] - unit_first_[lo + i] : 1;
+			return b;
+		};
 		if (P.anchors_only) { // the caller chains (RMQ): hand over the sorted anchors as they are
 			Anchor *ha = ln.h_anchors.ensure(n_a + 1);
 			uint64_t *hmp = ln.h_minipos.ensure(n_mp + 1);
@@ -389,6 +397,15 @@ public:
 			stream_wait(st);
 			Trace::get().add(lane_id, "gpu:expand+sort, d2h:anchors", tt, Trace::now());
 			kp.collect();
+			if (cdump) { // every read is handed back: the caller's blocks (mapper.cpp) hold the chains
+				std::string txt;
+				for (size_t i = 0; i < n; ++i) {
+					ChainDumpBlock b = dump_block(i);
+					b.handed_back = true, b.in = ha + a_off[i], b.n_in = (int64_t)(a_off[i + 1] - a_off[i]);
+					chain_dump_format(txt, P, b);
+				}
+				chain_dump_flush(cdump, txt);
+			}
 			parallel_for(n_threads, (long)n, [&](long i, int) {
 				ReadChains &c = out[i];
 				c.rep_len = h_rep[i];
@@ -449,6 +466,22 @@ public:
 			if (lazy && n_pos) HIP_CHECK(hipMemcpyAsync(hmp + mp_off[rd.first], ln.d_minipos.p + mp_off[rd.first], n_pos * 8, hipMemcpyDeviceToHost, st));
 		}
 		stream_wait(st);
+		if (cdump) { // the sorted anchors that went in and the first pass as the backtrack left it (with lazy chains the anchors are still on the device: copied here only)
+			std::vector<Anchor> all(n_a + 1), bt(lazy ? n_v + 1 : 0);
+			if (n_a) HIP_CHECK(hipMemcpyAsync(all.data(), ln.d_anchors.p, n_a * sizeof(Anchor), hipMemcpyDeviceToHost, st));
+			if (lazy && n_v) HIP_CHECK(hipMemcpyAsync(bt.data(), ln.d_bt_out_a.p, n_v * sizeof(Anchor), hipMemcpyDeviceToHost, st));
+			stream_wait(st);
+			const Anchor *chained = lazy ? bt.data() : ha;
+			std::string txt;
+			for (size_t i = 0; i < n; ++i) {
+				ChainDumpBlock b = dump_block(i);
+				b.in = all.data() + a_off[i], b.n_in = (int64_t)(a_off[i + 1] - a_off[i]);
+				b.handed_back = h_tie && h_tie[i];
+				if (!b.handed_back) b.u = hu + h_uoff[i], b.n_u = h_nu[i], b.a = chained + h_aoff[i], b.n_a = h_nv[i];
+				chain_dump_format(txt, P, b);
+			}
+			chain_dump_flush(cdump, txt);
+		}
 		Trace::get().add(lane_id, "d2h:chains", tt, Trace::now()); tt = Trace::now();
 		kp.collect();
 		TraceScope ts(lane_id, "host:chains->vectors");
@@ -468,7 +501,7 @@ public:
 			c.mp_p = hmp + mp_off[rd.first];
 			c.a_p = h_redo + rd.second, c.n_a = (int64_t)(a_off[rd.first + 1] - a_off[rd.first]);
 		}
-		if (P.long_join && !has_pairs_ && !getenv("MM2AMD_LONG_JOIN_ON_HOST")) long_join(P, lo, n, ln, kp, out, ha, hu, h_nu, h_nv, h_aoff, h_uoff, h_span); // (the diagnostic switch: every re-chain through rmq_chain.cpp)
+		if (P.long_join && !has_pairs_ && !getenv("MM2AMD_LONG_JOIN_ON_HOST")) long_join(P, lo, n, ln, kp, out, ha, hu, h_nu, h_nv, h_aoff, h_uoff, h_span, cdump); // (the diagnostic switch: every re-chain through rmq_chain.cpp)
 	}
 
 	// The chaining kernels give a wavefront to a read.  A read with far more anchors than the others (it crosses a multi-copy element of the reference) makes the whole
@@ -507,7 +540,7 @@ public:
 	// chain_rmq_kernel with bw_long, and the backtrack again.  A read the RMQ kernel hands back (a range minimum that is not unique, an
 	// over-full neighbourhood) keeps its first chains and long_join_done unset: the caller re-chains it with rmq_chain.cpp.
 	void long_join(const SeedChainParams &P, long lo, size_t n, Lane &ln, KernelProfiler &kp, std::vector<ReadChains> &out, const Anchor *ha, const uint64_t *hu,
-	               const int32_t *h_nu, const int32_t *h_nv, const uint64_t *h_aoff, const uint64_t *h_uoff, const int32_t *h_span)
+	               const int32_t *h_nu, const int32_t *h_nv, const uint64_t *h_aoff, const uint64_t *h_uoff, const int32_t *h_span, const char *cdump)
 	{
 		const bool lazy = h_span != nullptr; // (the chained anchors stayed on the device: the first chain's ends came back on their own)
 		hipStream_t st = ln.stream;
@@ -575,6 +608,25 @@ public:
 		ln.rg_n_v2 = n_v2, ln.rg_n_u2 = n_u2;
 		stream_wait(st);
 		kp.collect();
+		if (cdump) { // the second pass of the re-chained reads
+			std::vector<Anchor> bt(lazy ? n_v2 + 1 : 0);
+			if (lazy && n_v2) {
+				HIP_CHECK(hipMemcpyAsync(bt.data(), ln.d_lj_out_a.p, n_v2 * sizeof(Anchor), hipMemcpyDeviceToHost, st));
+				stream_wait(st);
+			}
+			const Anchor *chained = lazy ? bt.data() : ha2;
+			const Resident &R = res_[ln.set];
+			std::string txt;
+			for (size_t k = 0; k < n2; ++k) {
+				const size_t i = sel[k];
+				ChainDumpBlock b;
+				b.name = R.read_names.empty() ? nullptr : R.read_names[lo + i];
+				b.qlen = (int)(seq_off[lo + i + 1] - seq_off[lo + i]), b.pass = 2, b.handed_back = tie2[k] != 0;
+				if (!b.handed_back) b.u = hu2 + uoff2[k], b.n_u = nu2[k], b.a = chained + aoff2[k], b.n_a = nv2[k];
+				chain_dump_format(txt, P, b);
+			}
+			chain_dump_flush(cdump, txt);
+		}
 		for (size_t k = 0; k < n2; ++k) {
 			ReadChains &c = out[sel[k]];
 			if (tie2[k]) { c.long_join_done = false; continue; } // the host's tie-exact tree does this one

@@ -8,6 +8,7 @@
 #include <new>
 #include "mapper.hpp"
 #include "host_prof.hpp"
+#include "chain_dump.hpp"
 #include "chain_host.hpp"
 #include "threads.hpp"
 #include "trace.hpp"
@@ -434,6 +435,7 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 			SeedChainParams sp2 = sp;
 			sp2.mid_occ = opt_.max_occ;
 			sp2.long_join = 0; // map.c:293: this branch is the ELSE of the long-join: its chains are final
+			sp2.chain_dump = 0; // (MM2AMD_CHAIN_DUMP shows the first seeding only)
 			std::vector<ReadChains> second;
 			be_.seed_chain(sp2, lo, hi, lane, n_threads_, second);
 			for (long i : again) { chains[i] = second[i]; chains[i].take_ownership(); chains[i].long_join_done = true; }
@@ -505,6 +507,15 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 		}
 		if (ds.q4.size() < q4_total + 16) ds.q4.resize(q4_total + q4_total / 4 + 16); // (every strand block is followed by >= 15 bytes of its own: update_extra compares 16 columns per load, q4_stride)
 		std::atomic<long> n_lj_dev{0}, n_lj_host{0};
+		const char *cdump = chain_dump_path(); // diagnostics (chain_dump.hpp): the chains the host makes below, marked "host"
+		auto dump_host = [&](const ReadView &rv, int pass, const Anchor *in, int64_t n_in, const ReadChains &c) {
+			ChainDumpBlock b;
+			b.name = rv.name, b.qlen = rv.total(), b.n_seg = rv.paired() ? 2 : 1, b.pass = pass, b.host = true;
+			b.in = in, b.n_in = n_in, b.u = c.u_p, b.n_u = c.n_u, b.a = c.a_p, b.n_a = c.n_a;
+			std::string txt;
+			chain_dump_format(txt, sp, b);
+			chain_dump_flush(cdump, txt);
+		};
 		parallel_for(n_threads_, m, [&](long i, int) {
 			hostprof::Scope hp(hostprof::CHAINS_TO_HITS);
 			ReadChains &c = chains[i];
@@ -525,10 +536,13 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 				ChainScratch sc;
 				std::vector<uint64_t> u2;
 				std::vector<Anchor> out_a;
+				const Anchor *in_p = c.a_p; // (stays valid to the end of this block: the backend's buffer, or the vector swapped out below)
+				const int64_t in_n = c.n_a;
 				chain_rmq(opt_.max_gap, opt_.rmq_inner_dist, opt_.bw, opt_.max_chain_skip, opt_.rmq_size_cap, opt_.min_cnt, opt_.min_chain_score,
 				          sp.chn_pen_gap, sp.chn_pen_skip, c.n_a, c.a_p, u2, out_a, sc);
 				c.u.swap(u2), c.a.swap(out_a);
 				c.u_p = c.u.data(), c.n_u = (int32_t)c.u.size(), c.a_p = c.a.data(), c.n_a = (int64_t)c.a.size();
+				if (cdump) dump_host(rv, 1, in_p, in_n, c);
 			}
 			if (!c.long_join_done && opt_.bw_long > opt_.bw && (opt_.flag & (F_SPLICE | F_SR | F_NO_LJOIN)) == 0 && n_segs == 1 && c.n_u > 1) { // long-join re-chaining (map.c:283-292): the reads the backend left alone
 				const int32_t st = (int32_t)c.a_p[0].y, en = (int32_t)c.a_p[(int32_t)c.u_p[0] - 1].y;
@@ -542,6 +556,7 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 					          sp.chn_pen_gap, sp.chn_pen_skip, (int64_t)a2.size(), a2.data(), u2, out_a, sc);
 					c.u.swap(u2), c.a.swap(out_a);
 					c.u_p = c.u.data(), c.n_u = (int32_t)c.u.size(), c.a_p = c.a.data(), c.n_a = (int64_t)c.a.size();
+					if (cdump) dump_host(rv, 2, a2.data(), (int64_t)a2.size(), c);
 					++n_lj_host;
 				}
 			}
