@@ -21,8 +21,10 @@ extern "C" {
 #define MM2AMD_EHIP    (-3)   /* HIP runtime error */
 #define MM2AMD_ENOMEM  (-4)   /* a caller-provided pool was too small */
 #define MM2AMD_ESTATE  (-5)   /* called in the wrong state (e.g. map before init) */
+#define MM2AMD_EIO     (-6)   /* open/read/write failed; text carries strerror */
 
 const char *mm2amd_last_error(void);
+int mm2amd_last_error_code(void);         /* the MM2AMD_E* code that text belongs to (for the entry points that return a pointer) */
 int mm2amd_version(void);                 /* ABI version, currently 1 */
 int mm2amd_host_cpus(void);                     /* CPUs this process may use: hardware threads capped by the container's CPU quota (cgroup cpu.max); what n_threads <= 0 resolves against */
 int mm2amd_device_count(void);            /* number of visible HIP devices, or negative error */
@@ -140,6 +142,32 @@ int32_t mm2amd_idx_cal_max_occ(const mm2amd_index_t *idx, float f); /* mm_idx_ca
 int mm2amd_mapopt_update(void *mo, const mm2amd_index_t *idx);    /* mm_mapopt_update, options.c:69 */
 int mm2amd_idx_table_shape(const mm2amd_index_t *idx, int *bucket_bits, int *key_shift);
 int mm2amd_idx_export(const mm2amd_index_t *idx, uint32_t *bucket_start, uint64_t *keys, uint32_t *val_off, uint64_t *pos, uint32_t *S);
+
+/* ------------------------------------------------------------------------------------------------
+ * Index files: the device-built index written and read in the reference's .mmi format (MMI\2).
+ * A file written here loads with the unmodified reference (mm_idx_load, the minimap2 binary) and every section equals what
+ * mm_idx_dump writes for the index mm_idx_gen / mm_idx_str builds from the same sequences with the same w, k, b, flag -- magic and
+ * header, name/length table, per bucket n, the p array, size, and S -- with ONE exception: a bucket's (key, value) pairs are written
+ * in ascending key order, where the reference writes them in khash slot order (an artefact of its probing; mm_idx_load re-inserts
+ * them, so the loaded index is the same).
+ * ------------------------------------------------------------------------------------------------ */
+#define MM2AMD_DUMP_NO_SEQ 1                  /* write an MM_I_NO_SEQ index (no S section) */
+/* mm_idx_dump (index.c:475-514): one index part in the reference's MMI\2 format. bucket_bits <= 0: 14.  MM2AMD_EINVAL for what the
+ * format cannot hold (a name of more than 255 bytes, a bucket of 2^31 positions or more, bucket_bits outside [1, 2k] or above 28, an
+ * index without sequence unless MM2AMD_DUMP_NO_SEQ is given); MM2AMD_EIO when a write fails -- the partial file is removed. */
+int mm2amd_idx_dump(const mm2amd_index_t *idx, const char *fn, int bucket_bits, int flags);
+/* mm_idx_load (index.c:516-569) for part `part` (0-based) of a possibly multi-part file, as mm_idx_reader_read (index.c:621)
+ * walks them. *more (may be NULL) = 1 when another part follows the one loaded. NULL on failure (mm2amd_last_error_code():
+ * MM2AMD_EINVAL for a truncated or corrupt file or a part beyond the last, MM2AMD_EIO when the file cannot be opened or read).
+ * The tables come from the file's bucket records (they are not rebuilt from S); a file with MM_I_NO_SEQ gives an index that serves
+ * chain-level mapping only. */
+mm2amd_index_t *mm2amd_idx_load(const char *fn, int part, int *more);
+int mm2amd_idx_is_idx(const char *fn);        /* mm_idx_is_idx (index.c:571): 1 an index file, 0 not, <0 error */
+int mm2amd_idx_seq(const mm2amd_index_t *idx, uint32_t i, const char **name, uint32_t *len);  /* mi->seq[i]; name NULL with MM_I_NO_NAME */
+/* Diagnostics: the phases of this process' last mm2amd_idx_dump / mm2amd_idx_load -- total, regroup (dump: sort by bucket + offsets), serialise / unpack
+ * kernels, device<->host copies (HIP events), file write / read (host clock), sort and tables (load), of which S, then image bytes, file bytes, chunks,
+ * chunk bytes.  Milliseconds and bytes; returns the number of values there are. */
+int mm2amd_idx_io_stats(double *v, int n);
 
 /* Call once per index part after mm_mapopt_update() (main.c:465): builds the device mirror of the index
  * (flat minimizer table + 4-bit packed reference) and captures the mapping options.  n_threads sizes the host

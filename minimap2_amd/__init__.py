@@ -91,6 +91,9 @@ class KernelStat(C.Structure):  # mm2amd_kernel_stat_t
 assert C.sizeof(MapOpt) == 264 and C.sizeof(Reg1) == 80 and C.sizeof(Extra) == 28 and C.sizeof(Bseq1) == 40 and C.sizeof(IdxOpt) == 24
 
 F_CIGAR, F_OUT_SAM = 0x004, 0x008  # MM_F_CIGAR, MM_F_OUT_SAM (minimap.h:12-13)
+I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
+EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
+DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
 
 _lib = None
 
@@ -139,6 +142,12 @@ def _bind(L):
         L.mm2amd_mapopt_update.argtypes = [vp, vp]
         L.mm2amd_idx_table_shape.argtypes = [vp, ip, ip]
         L.mm2amd_idx_export.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.mm2amd_idx_dump.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
+        L.mm2amd_idx_load.restype = vp
+        L.mm2amd_idx_load.argtypes = [C.c_char_p, C.c_int, ip]
+        L.mm2amd_idx_is_idx.argtypes = [C.c_char_p]
+        L.mm2amd_idx_seq.argtypes = [vp, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32)]
+        L.mm2amd_idx_io_stats.argtypes = [C.POINTER(C.c_double), C.c_int]
         L.mm_gpu_init_index.argtypes = [vp, vp, C.c_int]
         L.mm_gpu_init_index_multi.argtypes = [vp, vp, C.c_int, C.c_int, ip]
         L.mm2amd_set_opt.argtypes = [C.c_char_p, vp, vp]
@@ -178,7 +187,89 @@ def lib(path=None):
 
 def _check(rc, L=None):
     if rc != 0:
-        raise Mm2AmdError("mm2amd error %d: %s" % (rc, (L or lib()).mm2amd_last_error().decode()))
+        e = Mm2AmdError("mm2amd error %d: %s" % (rc, (L or lib()).mm2amd_last_error().decode()))
+        e.code = rc
+        raise e
+
+
+# ---------------------------------------------------------------------------------------------------------
+# index files (.mmi) and sequence files
+# ---------------------------------------------------------------------------------------------------------
+def idx_is_idx(fn):
+    """mm_idx_is_idx: True when fn is a minimap2 index file, False when it is something else; raises when it cannot be opened"""
+    rc = lib().mm2amd_idx_is_idx(os.fsencode(fn))
+    if rc < 0:
+        _check(rc)
+    return rc == 1
+
+
+def idx_load(fn, part=0):
+    """mm2amd_idx_load: (index handle, more) for part `part` of a .mmi file; release the handle with idx_destroy()"""
+    L = lib()
+    more = C.c_int(0)
+    h = L.mm2amd_idx_load(os.fsencode(fn), part, C.byref(more))
+    if not h:
+        e = Mm2AmdError("mm2amd error %d: %s" % (L.mm2amd_last_error_code(), L.mm2amd_last_error().decode()))
+        e.code = L.mm2amd_last_error_code()
+        raise e
+    return h, bool(more.value)
+
+
+def idx_dump(idx, fn, bucket_bits=0, flags=0):
+    """mm2amd_idx_dump: the index behind the handle as one part of a .mmi file"""
+    _check(lib().mm2amd_idx_dump(idx, os.fsencode(fn), bucket_bits, flags))
+
+
+def idx_destroy(idx):
+    lib().mm2amd_idx_destroy(idx)
+
+
+def idx_io_stats():
+    """phases of the last idx_dump / idx_load of this process (milliseconds, bytes)"""
+    v = (C.c_double * 16)()
+    n = lib().mm2amd_idx_io_stats(v, 16)
+    names = ["total_ms", "regroup_ms", "kernel_ms", "copy_ms", "file_ms", "sort_ms", "tables_ms", "seq_ms", "image_bytes", "file_bytes", "n_chunks", "chunk_bytes"]
+    return dict(zip(names, list(v)[:n]))
+
+
+def read_fastx(fn):
+    """The records of a FASTA / FASTQ file, plain or gzip, as (names, sequences) -- lists of bytes; a name ends at the first blank, as kseq's does."""
+    import gzip
+    with open(fn, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    names, seqs = [], []
+    with (gzip.open(fn, "rb") if gz else open(fn, "rb")) as f:
+        data = f.read()
+    lines = data.split(b"\n")
+    i, n = 0, len(lines)
+    while i < n:
+        ln = lines[i].rstrip(b"\r")
+        i += 1
+        if not ln:
+            continue
+        if ln[:1] == b">":
+            names.append(ln[1:].split(None, 1)[0] if len(ln) > 1 and ln[1:].split() else b"")
+            parts = []
+            while i < n and lines[i][:1] not in (b">", b"@"):
+                parts.append(lines[i].strip())
+                i += 1
+            seqs.append(b"".join(parts))
+        elif ln[:1] == b"@":
+            names.append(ln[1:].split(None, 1)[0] if len(ln) > 1 and ln[1:].split() else b"")
+            parts, got = [], 0
+            while i < n and lines[i][:1] != b"+":
+                parts.append(lines[i].strip())
+                i += 1
+            seqs.append(b"".join(parts))
+            i += 1  # the '+' line
+            while i < n and got < len(seqs[-1]):  # as many quality characters as there are bases
+                got += len(lines[i].strip())
+                i += 1
+        else:
+            raise Mm2AmdError("%s: neither FASTA nor FASTQ (line %d)" % (fn, i))
+    if not seqs:
+        raise Mm2AmdError("%s: no sequence" % fn)
+    return names, seqs
 
 
 def update_extra_batch(jobs, mat, q, e, log_gap):
@@ -356,19 +447,20 @@ class Aligner(object):
     """Index built on the GPU from in-memory sequences + batched mapping; mirrors mappy.Aligner(seq=..., preset=...).
 
     seq: a sequence string/bytes or a list of them (the reference); names: optional list of contig names.
+    fn_idx_in: instead of seq, a file -- a minimap2 index (.mmi, read by mm2amd_idx_load; part: which part of a multi-part file, required when
+    there is more than one; the file's k, w and flags replace the preset's) or FASTA / FASTQ, plain or gzip.  fn_idx_out: write the index there
+    as a .mmi (mm2amd_idx_dump) once it is built.
     n_gpus / device_ids: map every batch on several GPUs of this process (mm_gpu_init_index_multi: index replicated, reads sharded
     by bases; an ordinal may repeat).  Only one Aligner can be the active mapper of the process at a time (the drop-in boundary is
     a process-wide context, like the reference's pipeline): creating a second one makes the first inactive -- its map calls raise,
     and closing or collecting it leaves the new context alone."""
 
-    def __init__(self, seq, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None):
+    def __init__(self, seq=None, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None,
+                 fn_idx_in=None, fn_idx_out=None, part=None):
         L = lib()
         self._generation, self._idx, self._staged = 0, None, None  # close() must work on a half-built object
-        seqs = [seq] if isinstance(seq, (bytes, str)) else list(seq)
-        self._seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
-        n = len(self._seqs)
-        self.names = [x if isinstance(x, str) else x.decode() for x in names] if names else ["ref%d" % i for i in range(n)]
-        self.lens = [len(s) for s in self._seqs]
+        if (seq is None) == (fn_idx_in is None):
+            raise Mm2AmdError("give exactly one of seq and fn_idx_in")
         self.idx_opt, self.map_opt = IdxOpt(), MapOpt()
         L.mm2amd_set_opt(None, C.byref(self.idx_opt), C.byref(self.map_opt))
         if preset is not None and L.mm2amd_set_opt(preset.encode(), C.byref(self.idx_opt), C.byref(self.map_opt)) != 0:
@@ -381,18 +473,53 @@ class Aligner(object):
             self.map_opt.flag |= F_CIGAR
         if sam:
             self.map_opt.flag |= F_OUT_SAM | F_CIGAR
+        from_index = fn_idx_in is not None and idx_is_idx(fn_idx_in)
+        if from_index:
+            # a prebuilt index: its k, w and flag win over the preset's, as in the reference's reader (mm_idx_reader_read, index.c:621-635)
+            self._idx, more = idx_load(fn_idx_in, part or 0)
+            if more and part is None:
+                raise Mm2AmdError("%s holds more than one index part: say which with part=" % fn_idx_in)
+            st = self.index_stat()
+            self.idx_opt.k, self.idx_opt.w, self.idx_opt.flag = st["k"], st["w"], st["flag"]
+            self._seqs = None
+            nm, ln = C.c_char_p(), C.c_uint32()
+            self.names, self.lens = [], []
+            for i in range(st["n_seq"]):
+                _check(L.mm2amd_idx_seq(self._idx, i, C.byref(nm), C.byref(ln)))
+                self.names.append(nm.value.decode() if nm.value is not None else None)
+                self.lens.append(ln.value)
+            self._name_bytes = None
+        else:
+            if fn_idx_in is not None:  # FASTA / FASTQ, plain or gzip
+                if part:
+                    raise Mm2AmdError("part= applies to index files")
+                file_names, seq = read_fastx(fn_idx_in)
+                names = names or file_names
+            seqs = [seq] if isinstance(seq, (bytes, str)) else list(seq)
+            self._seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+            n = len(self._seqs)
+            self.names = [x if isinstance(x, str) else x.decode() for x in names] if names else ["ref%d" % i for i in range(n)]
+            self.lens = [len(s) for s in self._seqs]
         _check(L.mm2amd_check_opt(C.byref(self.idx_opt), C.byref(self.map_opt)))
-        sarr = (C.c_char_p * n)(*self._seqs)
-        self._name_bytes = [x.encode() for x in self.names]
-        narr = (C.c_char_p * n)(*self._name_bytes)
-        self._idx = L.mm2amd_idx_str(self.idx_opt.w, self.idx_opt.k, self.idx_opt.flag & 1, self.idx_opt.bucket_bits, n, sarr, narr)
-        if not self._idx:
-            raise Mm2AmdError("index construction failed: %s" % L.mm2amd_last_error().decode())
+        if not from_index:
+            sarr = (C.c_char_p * n)(*self._seqs)
+            self._name_bytes = [x.encode() for x in self.names]
+            narr = (C.c_char_p * n)(*self._name_bytes)
+            self._idx = L.mm2amd_idx_str(self.idx_opt.w, self.idx_opt.k, self.idx_opt.flag & 1, self.idx_opt.bucket_bits, n, sarr, narr)
+            if not self._idx:
+                raise Mm2AmdError("index construction failed: %s" % L.mm2amd_last_error().decode())
+        if fn_idx_out is not None:
+            idx_dump(self._idx, fn_idx_out, self.idx_opt.bucket_bits, DUMP_NO_SEQ if self.index_stat()["flag"] & I_NO_SEQ else 0)
         _check(L.mm2amd_mapopt_update(C.byref(self.map_opt), self._idx))
         ids = (C.c_int * len(device_ids))(*device_ids) if device_ids else None
         _check(L.mm_gpu_init_index_multi(self._idx, C.byref(self.map_opt), n_threads, len(device_ids) if device_ids else n_gpus, ids))
         self._generation = L.mm_gpu_context_generation()
         self._staged = None
+
+    @property
+    def seq_names(self):
+        """the reference sequences' names, in index order (mappy.Aligner.seq_names)"""
+        return list(self.names)
 
     def _active(self):
         if lib().mm_gpu_context_generation() != self._generation:

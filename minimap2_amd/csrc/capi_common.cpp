@@ -39,11 +39,13 @@ void apply_hw_queue_default()
 	(void)once;
 }
 static thread_local std::string g_last_error;
+static thread_local int g_last_code = 0;
 void capi_set_error(const std::string &msg) { g_last_error = msg; }
-int capi_fail(int code, const std::string &msg) { g_last_error = msg; return code; }
+int capi_fail(int code, const std::string &msg) { g_last_error = msg; g_last_code = code; return code; }
 }
 extern "C" {
 const char *mm2amd_last_error(void) { return mm2amd::g_last_error.c_str(); }
+int mm2amd_last_error_code(void) { return mm2amd::g_last_code; }
 int mm2amd_version(void) { return 1; }
 int mm2amd_host_cpus(void) { return mm2amd::effective_cpus(); }
 }

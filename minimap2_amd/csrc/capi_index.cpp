@@ -1,5 +1,10 @@
 // Index and option entry points of the C ABI (include/mm2amd.h): in-memory index construction on the device
 // (mm_idx_str, index.c:421-470) and the option presets (options.c).
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <cerrno>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -102,11 +107,109 @@ int mm2amd_idx_export(const mm2amd_index_t *idx, uint32_t *bucket_start, uint64_
 		if (keys && h->T.n_keys) HIP_CHECK(hipMemcpy(keys, h->T.keys.p, h->T.n_keys * 8, hipMemcpyDeviceToHost));
 		if (val_off) HIP_CHECK(hipMemcpy(val_off, h->T.val_off.p, (h->T.n_keys + 1) * 4, hipMemcpyDeviceToHost));
 		if (pos && h->T.n_pos) HIP_CHECK(hipMemcpy(pos, h->T.pos.p, h->T.n_pos * 8, hipMemcpyDeviceToHost));
-		if (S) memcpy(S, h->fi.S, (h->fi.sum_len + 7) / 8 * 4);
+		if (S && h->fi.S) memcpy(S, h->fi.S, (h->fi.sum_len + 7) / 8 * 4); // (an index loaded from an MM_I_NO_SEQ file has none)
 		return 0;
 	} catch (const std::exception &e) {
 		return capi_fail(MM2AMD_EHIP, e.what());
 	}
+}
+
+/* ---- .mmi files (index_build.hip) ---- */
+
+int mm2amd_idx_dump(const mm2amd_index_t *idx, const char *fn, int bucket_bits, int flags)
+{
+	if (!idx || !fn) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_dump: null argument");
+	const IndexHandle *h = (const IndexHandle *)idx;
+	FILE *fp = nullptr;
+	int rc = 0;
+	try {
+		DeviceCtx &dc = device_ctx(h->device);
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		// what the format cannot hold is refused before the file is touched
+		if (bucket_bits <= 0) bucket_bits = 14;
+		if (bucket_bits > 2 * h->fi.k || bucket_bits > 28) throw std::invalid_argument("[mm2amd] index dump: bucket_bits must be in [1, 2k] and at most 28");
+		if (!(flags & MM2AMD_DUMP_NO_SEQ) && !h->fi.S) throw std::invalid_argument("[mm2amd] index dump: the index has no sequence (pass MM2AMD_DUMP_NO_SEQ)");
+		for (const std::string &nm : h->fi.names)
+			if (nm.size() > 255) throw std::invalid_argument("[mm2amd] index dump: sequence name longer than 255 bytes: " + nm.substr(0, 32) + "...");
+		fp = fopen(fn, "wb");
+		if (!fp) return capi_fail(MM2AMD_EIO, std::string("[mm2amd] index dump: cannot open ") + fn + ": " + strerror(errno));
+		DeviceIndexBuilder::dump(h->fi, h->T, fp, bucket_bits, (flags & MM2AMD_DUMP_NO_SEQ) != 0, dc.stream);
+		if (fclose(fp) != 0) { fp = nullptr; throw IdxIoError(std::string("[mm2amd] index dump: write failed: ") + strerror(errno)); }
+		return 0;
+	} catch (const IdxIoError &e) {
+		rc = capi_fail(MM2AMD_EIO, e.what());
+	} catch (const HipError &e) {
+		rc = capi_fail(MM2AMD_EHIP, e.what());
+	} catch (const std::exception &e) {
+		rc = capi_fail(MM2AMD_EINVAL, e.what());
+	}
+	if (fp) fclose(fp), remove(fn); // no partial file
+	else if (rc == MM2AMD_EIO) remove(fn);
+	return rc;
+}
+
+int mm2amd_idx_is_idx(const char *fn)
+{
+	if (!fn) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_is_idx: null file name");
+	if (strcmp(fn, "-") == 0) return 0;
+	const int fd = open(fn, O_RDONLY);
+	if (fd < 0) return capi_fail(MM2AMD_EIO, std::string("[mm2amd] cannot open ") + fn + ": " + strerror(errno));
+	char magic[4];
+	const ssize_t r = read(fd, magic, 4);
+	close(fd);
+	return r == 4 && memcmp(magic, "MMI\2", 4) == 0 ? 1 : 0;
+}
+
+mm2amd_index_t *mm2amd_idx_load(const char *fn, int part, int *more)
+{
+	if (more) *more = 0;
+	if (!fn || part < 0) { capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_load: need a file name and part >= 0"); return nullptr; }
+	const int fd = open(fn, O_RDONLY);
+	if (fd < 0) { capi_fail(MM2AMD_EIO, std::string("[mm2amd] index load: cannot open ") + fn + ": " + strerror(errno)); return nullptr; }
+	struct FdGuard { int fd; ~FdGuard() { close(fd); } } guard{fd};
+	try {
+		struct stat sb;
+		if (fstat(fd, &sb) != 0) throw IdxIoError(std::string("[mm2amd] index load: cannot stat ") + fn + ": " + strerror(errno));
+		const uint64_t file_size = (uint64_t)sb.st_size;
+		uint64_t off = 0;
+		for (int p = 0; p < part; ++p) off = DeviceIndexBuilder::skip_part(fd, file_size, off);
+		DeviceCtx &dc = device_ctx();
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		std::unique_ptr<IndexHandle> h(new IndexHandle);
+		h->device = dc.device_id;
+		const uint64_t end = DeviceIndexBuilder::load(h->fi, h->T, fd, file_size, off, dc.stream);
+		if (more) *more = end < file_size ? 1 : 0;
+		return (mm2amd_index_t *)h.release();
+	} catch (const IdxIoError &e) {
+		capi_fail(MM2AMD_EIO, e.what());
+	} catch (const HipError &e) {
+		const std::string s = e.what();
+		capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
+	} catch (const std::exception &e) {
+		capi_fail(MM2AMD_EINVAL, e.what());
+	}
+	return nullptr;
+}
+
+int mm2amd_idx_seq(const mm2amd_index_t *idx, uint32_t i, const char **name, uint32_t *len)
+{
+	if (!idx) return capi_fail(MM2AMD_EINVAL, "[mm2amd] null index");
+	const IndexHandle *h = (const IndexHandle *)idx;
+	if (i >= h->fi.n_seq) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_seq: no such sequence");
+	if (name) *name = (h->fi.flag & ref::I_NO_NAME) ? nullptr : h->fi.names[i].c_str();
+	if (len) *len = h->fi.seq_len[i];
+	return 0;
+}
+
+int mm2amd_idx_io_stats(double *v, int n)
+{
+	const IdxIoStats &s = idx_io_stats();
+	const double a[] = { s.total_ms, s.regroup_ms, s.kernel_ms, s.copy_ms, s.file_ms, s.sort_ms, s.tables_ms, s.seq_ms, s.image_bytes, s.file_bytes, s.n_chunks, s.chunk_bytes };
+	const int m = (int)(sizeof a / sizeof a[0]);
+	for (int i = 0; i < n && i < m; ++i) v[i] = a[i];
+	return m;
 }
 
 void mm2amd_idxopt_init(void *io) { idxopt_init((ref::IdxOpt *)io); }

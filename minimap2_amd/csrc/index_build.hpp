@@ -1,6 +1,8 @@
 // Device-resident index tables and their construction on the GPU (index_build.hip).
 #pragma once
 #include <cstdint>
+#include <cstdio>
+#include <stdexcept>
 #include <vector>
 #include "hip_util.hpp"
 #include "flat_index.hpp"
@@ -39,8 +41,26 @@ struct DeviceIndexBuilder {
 	// Same tables from an index that already carries its packed sequence (fi.S and the sequence table set: FlatIndex::from_reference
 	// without the host tables): the device part of mm_gpu_init.
 	static void build_from_packed(FlatIndex &fi, DeviceIndexTables &T, hipStream_t stream);
+	// One index part in the reference's MMI\2 format (mm_idx_dump, index.c:475-514), written to `fp`: the device regroups the flat
+	// tables by the low b hash bits and serialises the bucket section; the host writes header, names, the section's chunks and S.
+	// no_seq: an MM_I_NO_SEQ file (no S section).  Throws std::invalid_argument for what the format cannot hold, IdxIoError when a write fails.
+	static void dump(const FlatIndex &fi, const DeviceIndexTables &T, FILE *fp, int b, bool no_seq, hipStream_t stream);
+	// The reverse (mm_idx_load, index.c:516-569): the part that starts at file offset `off` of the file open as `fd` (`file_size`
+	// bytes long).  The tables come from the file's bucket records; every count is checked against the bytes that remain before it is
+	// believed.  Returns the offset the part ends at.  Throws std::invalid_argument for a corrupt file, IdxIoError when a read fails.
+	static uint64_t load(FlatIndex &fi, DeviceIndexTables &T, int fd, uint64_t file_size, uint64_t off, hipStream_t stream);
+	// Where the part at `off` ends, reading only its header, name table and bucket headers (the parts before the wanted one).
+	static uint64_t skip_part(int fd, uint64_t file_size, uint64_t off);
 private:
 	static void tables_from_nt4(FlatIndex &fi, DeviceIndexTables &T, DevBuf<uint8_t> &d_nt4, hipStream_t stream);
+	// step 4 of the build: distinct keys, value offsets, direct table, occurrence histogram and probe records from n_mz (hash, position)
+	// pairs sorted by (hash, position); T.pos takes d_pos over.  Returns the number of distinct keys.
+	static uint64_t tables_from_sorted(FlatIndex &fi, DeviceIndexTables &T, DevBuf<uint64_t> &d_hash, DevBuf<uint64_t> &d_pos, uint64_t n_mz, int k, hipStream_t stream);
 };
+
+struct IdxIoError : std::runtime_error { using std::runtime_error::runtime_error; }; // open / read / write failed (MM2AMD_EIO)
+// Phase times of the last dump or load of this process (diagnostics: tools/mm2amd_index.py --json): milliseconds and bytes
+struct IdxIoStats { double regroup_ms = 0, kernel_ms = 0, copy_ms = 0, file_ms = 0, sort_ms = 0, tables_ms = 0, total_ms = 0, image_bytes = 0, file_bytes = 0, n_chunks = 0, chunk_bytes = 0, seq_ms = 0; };
+IdxIoStats &idx_io_stats();
 
 } // namespace mm2amd
