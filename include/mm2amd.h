@@ -82,6 +82,27 @@ typedef struct { int32_t n_cigar, blen, mlen, n_ambi, dp_max, qshift, tshift, is
 int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
                               mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap);
 
+/* Alignment text on the device (aln_text_kernel, one wavefront per alignment): the per-base strings the reference writes hit by hit.
+ *   MM2AMD_TXT_CIGAR    "<len><op>" per operation, op letter from "MIDNSHP=XB" (write_sam_cigar, format.c)
+ *   MM2AMD_TXT_CS       the short cs string, identity runs as ":n" (write_cs_ds_core with no_iden = 1 and is_ds = 0, format.c:171-254)
+ *   MM2AMD_TXT_CS_LONG  the long cs string, identity runs as "=ACGT" (no_iden = 0)
+ *   MM2AMD_TXT_MD       the MD string (write_MD_core, format.c:302-331)
+ * without the "cs:Z:" / "MD:Z:" tag in front, as mm_gen_cs / mm_gen_MD (format.c:364-395) return them.  The ds string is not produced here.
+ * A job is one alignment: the aligned stretches as nt4 codes (0-3, 4 = N) and its CIGAR.  For cs / MD the operations must be M, I, D, N, = or
+ * X, none of length 0, no N shorter than 2, and they must cover exactly qlen and tlen (what the reference's asserts demand): a job that
+ * breaks this gets status -1 and no text, and the call still succeeds.  For MM2AMD_TXT_CIGAR only an operation above 9 is refused; the
+ * sequences are not read and may be NULL.
+ * The text of job i is pool[res[i].off, res[i].off + res[i].len), without a NUL; the jobs' texts follow each other in job order.
+ * pool == NULL sizes the batch: res[i].len and res[i].status are filled (the sum of the lengths is the pool the real call needs).
+ * A pool that is too small gives MM2AMD_ENOMEM with the lengths filled in; nothing is written at or beyond pool + pool_cap. */
+#define MM2AMD_TXT_CIGAR   0
+#define MM2AMD_TXT_CS      1
+#define MM2AMD_TXT_CS_LONG 2
+#define MM2AMD_TXT_MD      3
+typedef struct { const uint8_t *query, *target; int32_t qlen, tlen; const uint32_t *cigar; int32_t n_cigar; } mm2amd_txt_job_t;
+typedef struct { uint64_t off; uint32_t len; int32_t status; } mm2amd_txt_res_t;
+int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap);
+
 /* The two device-wide primitives of the index build (device_sort.hip), exposed for testing.  mm2amd_sort_pairs_u64: n (key, value) pairs
  * sorted in place by key bits [0, bits), stably -- what radix_sort_128x (ksort.h:101-151, instantiated at sketch.c:13 and called per bucket
  * at index.c:236) yields for pairs whose input order is ascending in the value: rs_hist / rs_chunk_scan / rs_block_offsets / rs_scatter
@@ -164,6 +185,17 @@ int mm2amd_idx_dump(const mm2amd_index_t *idx, const char *fn, int bucket_bits, 
 mm2amd_index_t *mm2amd_idx_load(const char *fn, int part, int *more);
 int mm2amd_idx_is_idx(const char *fn);        /* mm_idx_is_idx (index.c:571): 1 an index file, 0 not, <0 error */
 int mm2amd_idx_seq(const mm2amd_index_t *idx, uint32_t i, const char **name, uint32_t *len);  /* mi->seq[i]; name NULL with MM_I_NO_NAME */
+/* mm_idx_getseq (index.c:164-174): bases [st, en) of sequence rid as nt4 codes (0-3, 4 = N) into out; returns en - st.  MM2AMD_EINVAL for
+ * st > en, en beyond the sequence, a rid the index does not have, or an index without sequence (MM_I_NO_SEQ). */
+int mm2amd_idx_getseq(const mm2amd_index_t *idx, uint32_t rid, uint32_t st, uint32_t en, uint8_t *out);
+/* mm_gen_cs_ds_or_MD (format.c:333-375) for a batch of hits: the text `what` (MM2AMD_TXT_*, above) of hit[i] -- an mm_reg1_t* as
+ * mm_gpu_map_batch returns them -- whose read is qseq[i] (letters, qlen[i] of them).  The target comes from the handle's packed sequence on
+ * the device; the read's [qs, qe) letters are uploaded.  Orientation as format.c:343-358: is_qstrand = 0 writes on the target's strand (the
+ * read reverse-complemented for a hit on the reverse strand), is_qstrand = 1 on the read's (mm_idx_getseq2's window of the reverse strand).
+ * A hit without base-level alignment (p == NULL) gets len 0, status 0; res and pool as for mm2amd_aln_text_batch.  MM2AMD_EINVAL for an
+ * index without sequence, rid / rs / re outside the sequence, or qs / qe outside the read. */
+int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *const *hit, const char *const *qseq, const int32_t *qlen,
+                           int what, int is_qstrand, mm2amd_txt_res_t *res, char *pool, size_t pool_cap);
 /* Diagnostics: the phases of this process' last mm2amd_idx_dump / mm2amd_idx_load -- total, regroup (dump: sort by bucket + offsets), serialise / unpack
  * kernels, device<->host copies (HIP events), file write / read (host clock), sort and tables (load), of which S, then image bytes, file bytes, chunks,
  * chunk bytes.  Milliseconds and bytes; returns the number of values there are. */

@@ -33,6 +33,15 @@ class FinRes(C.Structure):  # mm2amd_fin_res_t
                 ("tshift", C.c_int32), ("is_spliced", C.c_int32), ("cigar_off", C.c_uint32)]
 
 
+class TxtJob(C.Structure):  # mm2amd_txt_job_t
+    _fields_ = [("query", C.c_void_p), ("target", C.c_void_p), ("qlen", C.c_int32), ("tlen", C.c_int32), ("cigar", C.POINTER(C.c_uint32)),
+                ("n_cigar", C.c_int32)]
+
+
+class TxtRes(C.Structure):  # mm2amd_txt_res_t
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("status", C.c_int32)]
+
+
 class KswRes(C.Structure):  # mm2amd_ksw_res_t
     _fields_ = [(n, C.c_int32) for n in ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score",
                                          "n_cigar", "reach_end")] + [("cigar_off", C.c_uint32)]
@@ -94,6 +103,7 @@ F_CIGAR, F_OUT_SAM = 0x004, 0x008  # MM_F_CIGAR, MM_F_OUT_SAM (minimap.h:12-13)
 I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
 EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
 DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
+TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD = 0, 1, 2, 3  # MM2AMD_TXT_*
 
 _lib = None
 
@@ -129,6 +139,10 @@ def _bind(L):
                                              C.POINTER(KswRes), C.POINTER(C.c_uint32), C.c_size_t]
         L.mm2amd_update_extra_batch.restype = C.c_int
         L.mm2amd_update_extra_batch.argtypes = [C.c_int, C.POINTER(FinJob), C.c_char_p, C.c_int8, C.c_int8, C.c_int, C.POINTER(FinRes), C.POINTER(C.c_uint32), C.c_size_t]
+        L.mm2amd_aln_text_batch.argtypes = [C.c_int, C.POINTER(TxtJob), C.c_int, C.POINTER(TxtRes), vp, C.c_size_t]
+        L.mm2amd_hits_text_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(TxtRes), vp,
+                                             C.c_size_t]
+        L.mm2amd_idx_getseq.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.mm2amd_sort_pairs_u64.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mm2amd_exclusive_sum_u32.argtypes = [vp, vp, C.c_uint64]
         L.mm2amd_idx_str.restype = vp
@@ -298,6 +312,45 @@ def update_extra_batch(jobs, mat, q, e, log_gap):
     return out
 
 
+def _texts(call, n):
+    """the sizing call, then the real one: a list of str, None for a job the kernel refused"""
+    res = (TxtRes * max(n, 1))()
+    _check(call(res, None, 0))
+    total = sum(r.len for r in res[:n])
+    pool = C.create_string_buffer(max(total, 1))
+    _check(call(res, pool, total))
+    raw = pool.raw
+    return [None if r.status != 0 else raw[r.off:r.off + r.len].decode("ascii") for r in res[:n]]
+
+
+def aln_text_batch(jobs, what):
+    """jobs: list of (query_codes, target_codes, cigar) -- nt4 codes 0..4 of the aligned stretches and the CIGAR as len << 4 | op words; the
+    sequences may be None for TXT_CIGAR.  what: TXT_CIGAR, TXT_CS, TXT_CS_LONG or TXT_MD.  Returns each job's text (what the reference's
+    mm_gen_cs / mm_gen_MD return, format.c:364-395; aln_text_kernel), or None for a job whose operations the kernel refuses."""
+    n = len(jobs)
+    arr = (TxtJob * max(n, 1))()
+    keep = []
+    for i, (q, t, cig) in enumerate(jobs):
+        qb, tb = (None if q is None else bytes(q)), (None if t is None else bytes(t))
+        ca = (C.c_uint32 * max(len(cig), 1))(*cig)
+        keep.append((qb, tb, ca))
+        arr[i].query, arr[i].target = C.cast(C.c_char_p(qb), C.c_void_p), C.cast(C.c_char_p(tb), C.c_void_p)
+        arr[i].qlen, arr[i].tlen, arr[i].cigar, arr[i].n_cigar = len(qb or b""), len(tb or b""), ca, len(cig)
+    L = lib()
+    return _texts(lambda res, pool, cap: L.mm2amd_aln_text_batch(n, arr, what, res, pool, cap), n)
+
+
+def hits_text(idx, hits, reads, what, is_qstrand=False):
+    """mm2amd_hits_text_batch: idx an index handle, hits the addresses of mm_reg1_t records, reads each hit's read (bytes).  Returns each
+    hit's text, '' for a hit without base-level alignment (mm_gen_cs_ds_or_MD, format.c:364-375)."""
+    n = len(hits)
+    harr = (C.c_void_p * max(n, 1))(*hits)
+    rb = [r.encode() if isinstance(r, str) else bytes(r) for r in reads]
+    qarr, qlen = (C.c_char_p * max(n, 1))(*rb), (C.c_int32 * max(n, 1))(*[len(r) for r in rb])
+    L = lib()
+    return _texts(lambda res, pool, cap: L.mm2amd_hits_text_batch(idx, n, harr, qarr, qlen, what, 1 if is_qstrand else 0, res, pool, cap), n)
+
+
 def sort_pairs_u64(keys, vals, bits=64):
     """(keys, vals) -- numpy uint64 arrays of equal length -- sorted by key bits [0, bits), stably, on the device (the index build's sort,
     device_sort.hip).  Returns new arrays."""
@@ -360,10 +413,13 @@ def ksw_extd2_batch(jobs, mat, gapo, gape, gapo2, gape2, noncan=None):
 # ---------------------------------------------------------------------------------------------------------
 # mappy-shaped front end
 # ---------------------------------------------------------------------------------------------------------
+_CODE_TO_BASE = bytes(b"ACGTN"[min(c, 4)] for c in range(256))
+
+
 class Alignment(object):
     """One hit; field names follow mappy.Alignment (python/mappy.pyx:30-90)."""
     __slots__ = ("ctg", "ctg_len", "r_st", "r_en", "q_st", "q_en", "strand", "mapq", "is_primary", "mlen", "blen", "NM",
-                 "cigar", "score", "dp_score", "rid", "sam_pri", "div", "parent", "id")
+                 "cigar", "score", "dp_score", "rid", "sam_pri", "div", "parent", "id", "cs", "MD")
 
     @property
     def cigar_str(self):
@@ -385,6 +441,7 @@ def _regs_to_alignments(n, regs, names, lens):
         a.strand = -1 if r.rev else 1
         a.mapq, a.is_primary, a.sam_pri = r.mapq, int(r.id == r.parent), r.sam_pri
         a.mlen, a.blen, a.score, a.div, a.parent, a.id = r.mlen, r.blen, r.score, r.div, r.parent, r.id
+        a.cs = a.MD = ""  # filled on request (Aligner.map_batch(cs=, MD=)), as mappy's
         if r.p:
             ex = r.p.contents
             a.dp_score = ex.dp_score
@@ -653,9 +710,10 @@ class Aligner(object):
             raise errors[0]
         return total[0]
 
-    def run(self, raw=False):
+    def run(self, raw=False, cs=False, MD=False):
         """Maps the staged batch.  Returns one list of alignments per read, or a pair of lists for a read pair.  raw=True returns
-        (n_reg, reg, rep_len) ctypes arrays (one entry per read, pairs adjacent) that must be passed to free_raw()."""
+        (n_reg, reg, rep_len) ctypes arrays (one entry per read, pairs adjacent) that must be passed to free_raw().
+        cs / MD: fill Alignment.cs (the short form) / Alignment.MD -- one mm2amd_hits_text_batch call per tag over all hits of the batch."""
         if self._staged is None:
             raise Mm2AmdError("run() without stage()")
         self._active()
@@ -672,7 +730,18 @@ class Aligner(object):
                 regs = C.cast(reg[k], C.POINTER(Reg1)) if n_reg[k] else None
                 per.append(_regs_to_alignments(n_reg[k], regs, self.names, self.lens))
             out.append(per[0] if n_seg[i] == 1 else tuple(per))
-        lib().mm2amd_free_regs(len(items), n_reg, reg)
+        try:
+            if cs or MD:
+                flat = [a for per in out for seg in (per if isinstance(per, tuple) else (per,)) for a in seg]  # read order, as the records below
+                segs = [k for i in range(n) for k in range(seg_off[i], seg_off[i] + n_seg[i])]
+                ptrs = [reg[k] + j * C.sizeof(Reg1) for k in segs for j in range(n_reg[k])]
+                rds = [items[k][1] for k in segs for j in range(n_reg[k])]
+                for want, what, field in ((cs, TXT_CS, "cs"), (MD, TXT_MD, "MD")):
+                    if want and ptrs:
+                        for a, t in zip(flat, hits_text(self._idx, ptrs, rds, what)):
+                            setattr(a, field, t or "")
+        finally:
+            lib().mm2amd_free_regs(len(items), n_reg, reg)
         return out
 
     def free_raw(self, n_reg, reg):
@@ -689,22 +758,38 @@ class Aligner(object):
         finally:
             _libc_free(out)
 
-    def map_batch(self, reads):
+    def map_batch(self, reads, cs=False, MD=False):
         self.stage(reads)
-        return self.run()
+        return self.run(cs=cs, MD=MD)
 
-    def map(self, seq, seq2=None, name="query"):
+    def map(self, seq, seq2=None, name="query", cs=False, MD=False):
         """Single-read (or, with seq2, single-pair) convenience wrapper (mappy.Aligner.map); a batch of one."""
         if seq2 is not None:
-            return self.map_pairs([(name, seq, seq2)])[0]
-        return self.map_batch([(name, seq)])[0]
+            return self.map_pairs([(name, seq, seq2)], cs=cs, MD=MD)[0]
+        return self.map_batch([(name, seq)], cs=cs, MD=MD)[0]
 
-    def map_pairs(self, pairs, text=False):
+    def seq(self, name, start=0, end=0x7fffffff):
+        """mappy.Aligner.seq (python/mappy.pyx:239, cmappy.h:122-138): bases [start, end) of the named reference sequence as str, end clipped
+        to the sequence; None for an unknown name, an empty range or an index without sequence (mm2amd_idx_getseq)."""
+        if not self._idx or self.index_stat()["flag"] & I_NO_SEQ or name not in self.names:
+            return None
+        rid = self.names.index(name)
+        if start < 0 or start >= self.lens[rid] or start >= end:
+            return None
+        end = min(end, self.lens[rid])
+        buf = C.create_string_buffer(end - start)
+        rc = lib().mm2amd_idx_getseq(self._idx, rid, start, end, buf)
+        if rc < 0:
+            _check(rc)
+        return buf.raw.translate(_CODE_TO_BASE).decode("ascii")
+
+    def map_pairs(self, pairs, text=False, cs=False, MD=False):
         """Paired-end reads: pairs = list of (name, seq1, seq2) (use preset "sr").  Returns a list of (alignments of read 1,
-        alignments of read 2); with text=True the SAM/PAF records of the batch instead (mm_gpu_format_batch, mate fields included)."""
+        alignments of read 2), with cs / MD filled on request; with text=True the SAM/PAF records of the batch instead
+        (mm_gpu_format_batch, mate fields included)."""
         self.stage(pairs)
         if not text:
-            return self.run()
+            return self.run(cs=cs, MD=MD)
         n_reg, reg, rep_len = self.run(raw=True)
         try:
             return self.format_raw(n_reg, reg, rep_len)

@@ -1,0 +1,275 @@
+// aln_text_kernel: see aln_text.hpp.  One wavefront per alignment; the lanes walk the alignment's COLUMNS 64 at a time.
+//
+//   columns   a base pair of an M / = / X operation is a column in every mode.  cs: every inserted and every deleted base is one, an intron
+//             (N) is ONE pseudo-column whatever its length.  MD: a deleted base is one; insertions and introns have none (the reference's
+//             counter runs across them).  One more column, the terminator, follows the last: it only flushes what is pending;
+//   staging   kTxtTileOps operations at a time go to LDS with their exclusive query / target / column offsets (three wave scans with
+//             carries); a lane finds the operation of its column there by bisection;
+//   runs      the text of a column may start with the length of the identity run that ends before it (cs ":n", MD "n").  A column that
+//             ends or starts a run publishes the column the next run starts at; an exclusive max-scan (carried from step to step) gives
+//             every column the start of the run it would flush, and so the run's length, without walking it;
+//   bytes     every lane runs the column emitter on a counting sink; wave_inclusive_sum (with a 64-bit carry) turns the counts into
+//             offsets.  The writing pass runs the SAME emitter again on a sink that stores into an LDS stage, placed so that the stage and
+//             the destination agree modulo 4, and the wave copies the stage out in aligned dwords (single bytes at the two ragged ends).
+//
+// The sizing pass validates first (64-bit sums: a CIGAR whose lengths wrap must not pass for one that covers the sequences), so that every
+// sequence index the walk forms lies inside [0, qlen) / [0, tlen).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "hip_util.hpp"
+#include "device_sort_dev.hpp"
+#include "aln_text.hpp"
+
+namespace mm2amd {
+
+#define TXT_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
+
+namespace {
+
+__device__ __forceinline__ int txt_ndigits(uint32_t v)
+{
+	return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
+}
+__device__ __forceinline__ int txt_lower(int c) { return (int)(0x6e74676361ull >> (c << 3) & 0xff); } // "acgtn"[c], c in 0..4
+__device__ __forceinline__ int txt_upper(int c) { return txt_lower(c) - 0x20; }                        // "ACGTN"[c]
+__device__ __forceinline__ int txt_nt4(uint32_t c) // kNt4Table (tables.cpp) without the table
+{
+	if (c < 4u) return (int)c;
+	const uint32_t l = c | 0x20u;
+	return l == 'a' ? 0 : l == 'c' ? 1 : l == 'g' ? 2 : (l == 't' || l == 'u') ? 3 : 4;
+}
+__device__ __forceinline__ uint32_t txt_inclusive_max(uint32_t v, int lane)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t u = __shfl_up(v, (unsigned)d);
+		if (lane >= d) v = u > v ? u : v;
+	}
+	return v;
+}
+
+struct TxtCount { // the sizing sink
+	uint32_t n = 0;
+	__device__ __forceinline__ void ch(int) { ++n; }
+	__device__ __forceinline__ void num(uint32_t v) { n += (uint32_t)txt_ndigits(v); }
+};
+struct TxtStore { // the writing sink: into the LDS stage
+	char *p;
+	__device__ __forceinline__ void ch(int c) { *p++ = (char)c; }
+	__device__ __forceinline__ void num(uint32_t v)
+	{
+		char *e = p + txt_ndigits(v);
+		p = e;
+		do { *--e = (char)('0' + v % 10u); v /= 10u; } while (v);
+	}
+};
+
+enum { TXT_NONE = 0, TXT_M, TXT_I, TXT_D, TXT_N, TXT_TERM };
+struct TxtCol {
+	int kind = TXT_NONE;
+	bool first = false, ident = false; // first column of its operation; query base == target base (by code: N against N is a match)
+	uint32_t pend = 0;                 // identity columns waiting to be flushed before this one
+	uint32_t len = 0;                  // N: the intron's length
+	int a = 4, b = 4, c = 4, d = 4;    // M: query, target base; I: a; D: b; N: the first two (a, b) and the last two (c, d) target bases
+};
+
+// The text of one column -- the only place that knows what cs, MD and CIGAR text look like; sizing and writing both go through it.
+template <class Sink>
+__device__ __forceinline__ void txt_emit_column(Sink &o, const TxtCol &k, int what)
+{
+	if (k.kind == TXT_NONE) return;
+	if (what == kTxtMd) { // write_MD_core, format.c:302-331
+		if (k.kind == TXT_M) { if (!k.ident) o.num(k.pend), o.ch(txt_upper(k.b)); }
+		else if (k.kind == TXT_D) { if (k.first) o.num(k.pend), o.ch('^'); o.ch(txt_upper(k.b)); }
+		else if (k.kind == TXT_TERM) { if (k.pend > 0) o.num(k.pend); }
+		return;
+	}
+	// write_cs_ds_core with is_ds == 0, format.c:171-254: an identity run ends at a mismatch and at the end of every M / = / X operation
+	const bool lng = what == kTxtCsLong;
+	if (!lng && k.pend > 0 && (!k.ident || k.first)) o.ch(':'), o.num(k.pend);
+	if (k.kind == TXT_M) {
+		if (!k.ident) o.ch('*'), o.ch(txt_lower(k.b)), o.ch(txt_lower(k.a));
+		else if (lng) { if (k.first || k.pend == 0) o.ch('='); o.ch(txt_upper(k.a)); }
+	} else if (k.kind == TXT_I) { if (k.first) o.ch('+'); o.ch(txt_lower(k.a)); }
+	else if (k.kind == TXT_D) { if (k.first) o.ch('-'); o.ch(txt_lower(k.b)); }
+	else if (k.kind == TXT_N) o.ch('~'), o.ch(txt_lower(k.a)), o.ch(txt_lower(k.b)), o.num(k.len), o.ch(txt_lower(k.c)), o.ch(txt_lower(k.d));
+}
+template <class Sink>
+__device__ __forceinline__ void txt_emit_cigar(Sink &o, uint32_t w) { o.num(w >> 4), o.ch("MIDNSHP=XB"[w & 0xf]); } // write_sam_cigar; w & 15 <= 9
+
+// n bytes of the stage, which start at stage byte `a` (= dst & 3), go to dst: whole dwords where both sides are aligned, bytes at the ends.
+// Nothing outside [dst, dst + n) is written.
+__device__ __forceinline__ void txt_copy_out(const uint32_t *stage, uint32_t a, uint32_t n, char *dst, int lane)
+{
+	const char *sb = (const char *)stage;
+	char *gb = dst - a; // 4-byte aligned
+	const uint32_t end = a + n, ndw = (end + 3u) >> 2;
+	for (uint32_t j = (uint32_t)lane; j < ndw; j += 64u) {
+		const uint32_t lo = j << 2, hi = lo + 4u;
+		if (lo >= a && hi <= end) *(uint32_t *)(gb + lo) = stage[j];
+		else for (uint32_t b = lo > a ? lo : a, e = hi < end ? hi : end; b < e; ++b) gb[b] = sb[b];
+	}
+}
+
+} // namespace
+
+template <bool WRITE>
+__global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
+{
+	__shared__ uint32_t s_word[kTxtTileOps], s_q[kTxtTileOps], s_t[kTxtTileOps], s_col[kTxtTileOps];
+	__shared__ uint32_t s_stage[(64 * kTxtColBytes + 4 + 3) / 4 + 1];
+	const int lane = (int)threadIdx.x;
+	const int id = (int)blockIdx.x;
+	const TxtJob J = P.jobs[id];
+	const int what = P.what;
+	const uint32_t n = J.n_cigar;
+	const uint32_t *cg = P.cigar + J.cig_off;
+	const bool md = what == kTxtMd;
+
+	if (WRITE) { // the sizing pass has judged the job
+		const TxtRes r = P.res[id];
+		if (r.status != 0 || r.len == 0) return;
+	} else {
+		bool bad = false;
+		unsigned long long sq = 0, st = 0;
+		for (uint32_t k = (uint32_t)lane; k < n; k += 64u) {
+			const uint32_t w = cg[k], op = w & 0xf, len = w >> 4;
+			if (what == kTxtCigar) { bad |= op > 9u; continue; }
+			bad |= !(op <= 3u || op == 7u || op == 8u) || len == 0u || (op == 3u && len < 2u);
+			if (op == 0u || op == 7u || op == 8u) sq += len, st += len;
+			else if (op == 1u) sq += len;
+			else if (op == 2u || op == 3u) st += len;
+		}
+		if (what != kTxtCigar) {
+#pragma unroll
+			for (int d = 32; d > 0; d >>= 1) sq += __shfl_xor(sq, d, 64), st += __shfl_xor(st, d, 64);
+			bad |= J.qlen < 0 || J.tlen < 0 || sq != (unsigned long long)(long long)J.qlen || st != (unsigned long long)(long long)J.tlen;
+		}
+		if (__ballot(bad) != 0ull) { // (an invalid job writes nothing but its own result)
+			if (lane == 0) { TxtRes r; r.cols = 0, r.len = 0, r.status = -1; P.res[id] = r; }
+			return;
+		}
+	}
+
+	unsigned long long nbytes = 0; // text so far (the same in every lane)
+	char *const out = WRITE ? P.out + P.off[id] : nullptr;
+	// one step's text: every lane has counted its bytes; offsets by a wave scan; the writing pass stages and copies out
+	auto place = [&](uint32_t mine, uint32_t &a, uint32_t &excl) -> uint32_t {
+		const uint32_t incl = wave_inclusive_sum(mine, lane);
+		excl = incl - mine;
+		a = WRITE ? (uint32_t)((uintptr_t)(out + nbytes) & 3u) : 0u;
+		return (uint32_t)__shfl((int)incl, 63, 64);
+	};
+	auto flush = [&](uint32_t a, uint32_t tot) {
+		if (WRITE) {
+			TXT_SYNC();
+			txt_copy_out(s_stage, a, tot, out + nbytes, lane);
+			TXT_SYNC();
+		}
+		nbytes += tot;
+	};
+
+	if (what == kTxtCigar) {
+		for (uint32_t k0 = 0; k0 < n; k0 += 64u) {
+			const uint32_t k = k0 + (uint32_t)lane;
+			const uint32_t w = k < n ? cg[k] : 0u;
+			TxtCount cnt;
+			if (k < n) txt_emit_cigar(cnt, w);
+			uint32_t a, excl;
+			const uint32_t tot = place(cnt.n, a, excl);
+			if (WRITE && k < n) { TxtStore s; s.p = (char *)s_stage + a + excl; txt_emit_cigar(s, w); }
+			flush(a, tot);
+		}
+		if (!WRITE && lane == 0) { TxtRes r; r.cols = n, r.len = (uint32_t)nbytes, r.status = nbytes > 0xffffffffull ? -1 : 0; if (r.status) r.len = 0; P.res[id] = r; }
+		return;
+	}
+
+	const uint32_t qlen = (uint32_t)J.qlen, tlen = (uint32_t)J.tlen;
+	auto qbase = [&](uint32_t i) -> int {
+		if (J.qsrc == kTxtQCodes) { const int c = P.qpool[J.q_pos + i]; return c > 4 ? 4 : c; }
+		if (J.qsrc == kTxtQAscii) return txt_nt4(P.qpool[J.q_pos + i]);
+		const int c = txt_nt4(P.qpool[J.q_pos + (qlen - 1u - i)]);
+		return c >= 4 ? 4 : 3 - c;
+	};
+	auto tbase = [&](uint32_t i) -> int {
+		if (J.tsrc == kTxtTCodes) { const int c = P.tpool[J.t_pos + i]; return c > 4 ? 4 : c; }
+		const uint64_t o = J.t_pos + (J.tsrc == kTxtTPacked ? i : tlen - 1u - i);
+		const int c = (int)(P.S[o >> 3] >> ((o & 7) << 2) & 0xf);
+		return J.tsrc == kTxtTPacked ? (c > 4 ? 4 : c) : (c < 4 ? 3 - c : 4);
+	};
+
+	uint32_t cq = 0, ct = 0, ccol = 0; // what the operations staged so far consume: query, target, columns
+	uint32_t run_from = 0;             // the column the pending identity run starts at (max over the columns walked so far)
+	// one step: the lane's column c (or none) -> its text
+	auto step = [&](bool active, uint32_t c, uint32_t nt, bool term) {
+		TxtCol k;
+		uint32_t next_run = 0; // where a run that follows this column starts: 0 = this column says nothing
+		if (active && term) k.kind = TXT_TERM;
+		else if (active) {
+			uint32_t lo = 0, hi = nt; // the last staged operation that starts at or before c (operations without columns never hold one)
+			while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (s_col[mid] <= c) lo = mid; else hi = mid; }
+			const uint32_t w = s_word[lo], op = w & 0xf, j = c - s_col[lo];
+			k.first = j == 0u;
+			if (op == 1u) k.kind = TXT_I, k.a = qbase(s_q[lo] + j);
+			else if (op == 2u) k.kind = TXT_D, k.b = tbase(s_t[lo] + j);
+			else if (op == 3u) {
+				const uint32_t t0 = s_t[lo];
+				k.kind = TXT_N, k.len = w >> 4;
+				k.a = tbase(t0), k.b = tbase(t0 + 1u), k.c = tbase(t0 + k.len - 2u), k.d = tbase(t0 + k.len - 1u);
+			} else k.kind = TXT_M, k.a = qbase(s_q[lo] + j), k.b = tbase(s_t[lo] + j), k.ident = k.a == k.b;
+			if (md) next_run = k.ident ? 0u : c + 1u;          // a mismatch or a deleted base: the count starts again behind it
+			else next_run = !k.ident ? c + 1u : k.first ? c : 0u; // cs: ... and an operation's first column starts a run of its own
+		}
+		const uint32_t incl = txt_inclusive_max(next_run, lane);
+		uint32_t before = __shfl_up(incl, 1u);
+		if (lane == 0) before = 0;
+		before = before > run_from ? before : run_from;
+		const uint32_t last = (uint32_t)__shfl((int)incl, 63, 64);
+		run_from = last > run_from ? last : run_from;
+		if (active) k.pend = c - before;
+		TxtCount cnt;
+		txt_emit_column(cnt, k, what);
+		uint32_t a, excl;
+		const uint32_t tot = place(cnt.n, a, excl);
+		if (WRITE && cnt.n) { TxtStore s; s.p = (char *)s_stage + a + excl; txt_emit_column(s, k, what); }
+		flush(a, tot);
+	};
+
+	for (uint32_t tile0 = 0; tile0 < n; tile0 += (uint32_t)kTxtTileOps) {
+		const uint32_t nt = n - tile0 < (uint32_t)kTxtTileOps ? n - tile0 : (uint32_t)kTxtTileOps;
+		const uint32_t col0 = ccol;
+		TXT_SYNC(); // (the steps of the tile before have read the arrays)
+		for (uint32_t r = 0; r < nt; r += 64u) {
+			const uint32_t i = r + (uint32_t)lane;
+			uint32_t w = 0, dq = 0, dt = 0, dc = 0;
+			if (i < nt) {
+				w = cg[tile0 + i];
+				const uint32_t op = w & 0xf, len = w >> 4;
+				if (op == 1u) dq = len, dc = md ? 0u : len;
+				else if (op == 2u) dt = len, dc = len;
+				else if (op == 3u) dt = len, dc = md ? 0u : 1u;
+				else dq = dt = dc = len;
+			}
+			const uint32_t iq = wave_inclusive_sum(dq, lane), it = wave_inclusive_sum(dt, lane), ic = wave_inclusive_sum(dc, lane);
+			if (i < nt) s_word[i] = w, s_q[i] = cq + iq - dq, s_t[i] = ct + it - dt, s_col[i] = ccol + ic - dc;
+			cq += (uint32_t)__shfl((int)iq, 63, 64), ct += (uint32_t)__shfl((int)it, 63, 64), ccol += (uint32_t)__shfl((int)ic, 63, 64);
+		}
+		TXT_SYNC();
+		for (unsigned long long c0 = col0; c0 < ccol; c0 += 64ull) { // (64 bits: columns may reach 2^32 - 2)
+			const unsigned long long c = c0 + (unsigned long long)lane;
+			step(c < ccol, (uint32_t)c, nt, false);
+		}
+	}
+	step(lane == 0, ccol, 0u, true); // the terminator
+	if (!WRITE && lane == 0) { TxtRes r; r.cols = ccol, r.len = (uint32_t)nbytes, r.status = nbytes > 0xffffffffull ? -1 : 0; if (r.status) r.len = 0; P.res[id] = r; }
+}
+
+void aln_text_launch(const TxtParams &P, bool write, void *stream)
+{
+	if (P.n_jobs <= 0) return;
+	if (write) hipLaunchKernelGGL(aln_text_kernel<true>, dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
+	else hipLaunchKernelGGL(aln_text_kernel<false>, dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
+	HIP_CHECK(hipGetLastError());
+}
+
+} // namespace mm2amd

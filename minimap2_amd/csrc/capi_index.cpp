@@ -15,9 +15,12 @@
 #include "index_build.hpp"
 #include "index_handle.hpp"
 #include "options.hpp"
+#include "aln_text.hpp"
 
 namespace mm2amd {
 int capi_fail(int code, const std::string &msg);
+int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const std::vector<uint8_t> &hq, const std::vector<uint8_t> &ht, const uint32_t *dS,
+                 const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool, size_t pool_cap); // capi_kernels.cpp
 struct IndexHandle {
 	FlatIndex fi;
 	DeviceIndexTables T;
@@ -201,6 +204,69 @@ int mm2amd_idx_seq(const mm2amd_index_t *idx, uint32_t i, const char **name, uin
 	if (name) *name = (h->fi.flag & ref::I_NO_NAME) ? nullptr : h->fi.names[i].c_str();
 	if (len) *len = h->fi.seq_len[i];
 	return 0;
+}
+
+int mm2amd_idx_getseq(const mm2amd_index_t *idx, uint32_t rid, uint32_t st, uint32_t en, uint8_t *out)
+{
+	if (!idx) return capi_fail(MM2AMD_EINVAL, "[mm2amd] null index");
+	const IndexHandle *h = (const IndexHandle *)idx;
+	if ((h->fi.flag & ref::I_NO_SEQ) || !h->fi.S) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_getseq: the index holds no sequence");
+	if (rid >= h->fi.n_seq || st > en || en > h->fi.seq_len[rid] || (en > st && !out)) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_getseq: no such sequence or range");
+	h->fi.getseq(rid, st, en, out);
+	return (int)(en - st);
+}
+
+int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *const *hit, const char *const *qseq, const int32_t *qlen,
+                           int what, int is_qstrand, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
+{
+	if (!idx) return capi_fail(MM2AMD_EINVAL, "[mm2amd] null index");
+	if (n_hits < 0 || (n_hits > 0 && (!hit || !qseq || !qlen || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_MD) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: bad arguments");
+	const IndexHandle *h = (const IndexHandle *)idx;
+	const FlatIndex &fi = h->fi;
+	if ((fi.flag & ref::I_NO_SEQ) || !fi.S || !h->T.S.p) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: the index holds no sequence");
+	if (n_hits == 0) return 0;
+	try {
+		std::vector<TxtJob> tj(n_hits);
+		size_t qtot = 0, ctot = 0;
+		for (int i = 0; i < n_hits; ++i) {
+			const ref::Reg1 *r = (const ref::Reg1 *)hit[i];
+			TxtJob &o = tj[i];
+			memset(&o, 0, sizeof o);
+			if (!r) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: null hit");
+			if (!r->p) continue; // no base-level alignment: the reference writes nothing (format.c:339)
+			if (r->rid < 0 || (uint32_t)r->rid >= fi.n_seq || r->rs < 0 || r->rs > r->re || (uint32_t)r->re > fi.seq_len[r->rid])
+				return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: a hit lies outside its reference sequence");
+			if (r->qs < 0 || r->qs > r->qe || r->qe > qlen[i] || (r->qe > r->qs && !qseq[i])) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: a hit lies outside its read");
+			const uint64_t so = fi.seq_off[r->rid];
+			o.q_pos = qtot, o.cig_off = ctot, o.n_cigar = r->p->n_cigar, o.qlen = r->qe - r->qs, o.tlen = r->re - r->rs;
+			if (is_qstrand) { // format.c:343-346: mm_idx_getseq2's window, the read as it is
+				o.qsrc = (uint8_t)kTxtQAscii;
+				o.tsrc = (uint8_t)(r->rev ? kTxtTPackedRev : kTxtTPacked);
+				o.t_pos = r->rev ? so + (fi.seq_len[r->rid] - (uint32_t)r->re) : so + (uint32_t)r->rs;
+			} else { // format.c:347-358
+				o.qsrc = (uint8_t)(r->rev ? kTxtQAsciiRev : kTxtQAscii);
+				o.tsrc = (uint8_t)kTxtTPacked, o.t_pos = so + (uint32_t)r->rs;
+			}
+			qtot += (size_t)o.qlen, ctot += (size_t)o.n_cigar;
+		}
+		std::vector<uint8_t> hq(qtot), ht;
+		std::vector<uint32_t> cig(ctot);
+		for (int i = 0; i < n_hits; ++i) {
+			const ref::Reg1 *r = (const ref::Reg1 *)hit[i];
+			if (!r->p) continue;
+			if (tj[i].qlen) memcpy(&hq[tj[i].q_pos], qseq[i] + r->qs, (size_t)tj[i].qlen);
+			if (tj[i].n_cigar) memcpy(&cig[tj[i].cig_off], r->p->cigar, (size_t)tj[i].n_cigar * 4);
+		}
+		DeviceCtx &dc = device_ctx(h->device);
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		return aln_text_run(dc, tj, what, hq, ht, h->T.S.p, cig, res, pool, pool_cap);
+	} catch (const HipError &e) {
+		const std::string s = e.what();
+		return capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
+	} catch (const std::exception &e) {
+		return capi_fail(MM2AMD_EINVAL, e.what());
+	}
 }
 
 int mm2amd_idx_io_stats(double *v, int n)

@@ -9,6 +9,7 @@
 #include "ksw_host.hpp"
 #include "kernel_prof.hpp"
 #include "region_finish.hpp"
+#include "aln_text.hpp"
 #include "device_sort.hpp"
 #include <map>
 
@@ -39,6 +40,63 @@ int guarded(F &&f)
 }
 
 } // namespace
+
+namespace mm2amd {
+
+// The two passes of aln_text_kernel around the host's offsets; shared by mm2amd_aln_text_batch and mm2amd_hits_text_batch (capi_index.cpp).
+// The caller holds dc.mu and has made the device current.  hq / ht: the jobs' byte pools (q_pos / t_pos of the kTxtQ* / kTxtTCodes sources
+// index them); dS: a packed reference already on the device (kTxtTPacked*), or null.
+int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const std::vector<uint8_t> &hq, const std::vector<uint8_t> &ht, const uint32_t *dS,
+                 const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
+{
+	const int n_jobs = (int)jobs.size();
+	DevBuf<uint8_t> d_q, d_t;
+	DevBuf<uint32_t> d_cig;
+	DevBuf<TxtJob> d_jobs;
+	DevBuf<TxtRes> d_res;
+	DevBuf<uint64_t> d_off;
+	DevBuf<char> d_out;
+	d_q.ensure(hq.size() + 1), d_t.ensure(ht.size() + 1), d_cig.ensure(cig.size() + 1), d_jobs.ensure(n_jobs), d_res.ensure(n_jobs), d_off.ensure(n_jobs);
+	if (!hq.empty()) HIP_CHECK(hipMemcpyAsync(d_q.p, hq.data(), hq.size(), hipMemcpyHostToDevice, dc.stream));
+	if (!ht.empty()) HIP_CHECK(hipMemcpyAsync(d_t.p, ht.data(), ht.size(), hipMemcpyHostToDevice, dc.stream));
+	if (!cig.empty()) HIP_CHECK(hipMemcpyAsync(d_cig.p, cig.data(), cig.size() * 4, hipMemcpyHostToDevice, dc.stream));
+	HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)n_jobs * sizeof(TxtJob), hipMemcpyHostToDevice, dc.stream));
+	TxtParams P;
+	P.jobs = d_jobs.p, P.n_jobs = n_jobs, P.what = what, P.qpool = d_q.p, P.tpool = d_t.p, P.S = dS, P.cigar = d_cig.p, P.res = d_res.p, P.off = nullptr, P.out = nullptr;
+	KernelProfiler &prof = kernel_profiler(0);
+	prof.begin(dc.stream);
+	aln_text_launch(P, false, dc.stream);
+	prof.end(dc.stream, "aln_text_kernel[size]", 0.0, 0.0);
+	std::vector<TxtRes> hr(n_jobs);
+	HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(TxtRes), hipMemcpyDeviceToHost, dc.stream));
+	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	std::vector<uint64_t> off(n_jobs);
+	uint64_t total = 0;
+	double cols = 0;
+	for (int i = 0; i < n_jobs; ++i) {
+		off[i] = total;
+		res[i].off = total, res[i].len = hr[i].len, res[i].status = hr[i].status;
+		total += hr[i].len, cols += (double)hr[i].cols;
+	}
+	prof.add_units("aln_text_kernel[size]", cols);
+	if (!pool || total > pool_cap || total == 0) {
+		prof.collect();
+		if (pool && total > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] alignment text: pool too small (a call with pool == NULL gives the lengths)");
+		return 0;
+	}
+	d_out.ensure(total, 1.0);
+	HIP_CHECK(hipMemcpyAsync(d_off.p, off.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, dc.stream));
+	P.off = d_off.p, P.out = d_out.p;
+	prof.begin(dc.stream);
+	aln_text_launch(P, true, dc.stream);
+	prof.end(dc.stream, "aln_text_kernel[write]", (double)total, cols);
+	HIP_CHECK(hipMemcpyAsync(pool, d_out.p, total, hipMemcpyDeviceToHost, dc.stream));
+	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	prof.collect();
+	return 0;
+}
+
+} // namespace mm2amd
 
 extern "C" {
 
@@ -193,6 +251,39 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
 		}
 		if (out_words) memcpy(cigar_pool, ho.data(), out_words * 4);
 		return 0;
+	});
+}
+
+int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
+{
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_MD) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad arguments");
+	if (n_jobs == 0) return 0;
+	return guarded([&]() -> int {
+		const bool seqs = what != MM2AMD_TXT_CIGAR;
+		std::vector<TxtJob> tj(n_jobs);
+		size_t qtot = 0, ttot = 0, ctot = 0;
+		for (int i = 0; i < n_jobs; ++i) {
+			const mm2amd_txt_job_t &j = jobs[i];
+			if (j.n_cigar < 0 || (j.n_cigar > 0 && !j.cigar)) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad job");
+			if (seqs && (j.qlen < 0 || j.tlen < 0 || (j.qlen > 0 && !j.query) || (j.tlen > 0 && !j.target))) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad job");
+			TxtJob &o = tj[i];
+			o.q_pos = qtot, o.t_pos = ttot, o.cig_off = ctot, o.n_cigar = (uint32_t)j.n_cigar, o.qlen = seqs ? j.qlen : 0, o.tlen = seqs ? j.tlen : 0;
+			o.qsrc = (uint8_t)kTxtQCodes, o.tsrc = (uint8_t)kTxtTCodes, o.reserved = 0;
+			ctot += (size_t)j.n_cigar;
+			if (seqs) qtot += (size_t)j.qlen, ttot += (size_t)j.tlen;
+		}
+		std::vector<uint8_t> hq(qtot), ht(ttot);
+		std::vector<uint32_t> cig(ctot);
+		for (int i = 0; i < n_jobs; ++i) {
+			const mm2amd_txt_job_t &j = jobs[i];
+			if (j.n_cigar) memcpy(&cig[tj[i].cig_off], j.cigar, (size_t)j.n_cigar * 4);
+			if (seqs && j.qlen) memcpy(&hq[tj[i].q_pos], j.query, (size_t)j.qlen);
+			if (seqs && j.tlen) memcpy(&ht[tj[i].t_pos], j.target, (size_t)j.tlen);
+		}
+		DeviceCtx &dc = device_ctx();
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		return aln_text_run(dc, tj, what, hq, ht, nullptr, cig, res, pool, pool_cap);
 	});
 }
 

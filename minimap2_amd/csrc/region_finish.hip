@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "hip_util.hpp"
 #include "region_finish.hpp"
+#include "aln_text_dev.hpp" // aln_text_kernel (the alignment's text: CIGAR string, cs, MD) is compiled with this translation unit
 
 namespace mm2amd {
 
