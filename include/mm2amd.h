@@ -103,6 +103,37 @@ typedef struct { const uint8_t *query, *target; int32_t qlen, tlen; const uint32
 typedef struct { uint64_t off; uint32_t len; int32_t status; } mm2amd_txt_res_t;
 int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap);
 
+/* Batched ksw_ll_qinit + ksw_ll_i16 (ksw2_ll_sse.c:37-152, ksw2.h:93-94): the local (Smith-Waterman) score of a pair with the end coordinates the
+ * reference reports -- te the LAST target row whose maximum equals the final maximum, qe the last slot of the 8-lane striped scan that holds it in
+ * that row -- as minimap2 uses it for the inversion test (align.c:84-101), mm_seed_ext_score (align.c:591-636) and mm_align1_inv (align.c:916-971).
+ * query / target: nt4 codes (0-3, 4 = N) in host memory; mat: the m x m score matrix, m = 5, target code a against query code b scores
+ * mat[a * m + b]; gapo, gape: a gap of length l costs gapo + l * gape.  flag says how the kernel reads the sequences, so that a caller needs no
+ * staging pass: MM2AMD_LL_QREV the query backwards, MM2AMD_LL_QCOMP the query complemented (code c < 4 becomes 3 - c, anything else 4; both
+ * together are the reverse complement of align.c:91-96), MM2AMD_LL_TREV the target backwards (with MM2AMD_LL_QREV: align.c:938-941).  res[i] is
+ * what ksw_ll_qinit(km, 2, ...) + ksw_ll_i16 return on the sequences so transformed, coordinates in those sequences; qe may be >= qlen when
+ * nothing scores (the scan's last slot is padding).  res[i].path says where job i ran -- the routing is a function of the job alone:
+ *   MM2AMD_LL_PATH_HOST  by the host's scalar routine inside the call: a job outside the class in which the plain affine recurrence equals the
+ *                        striped scan (it needs -min(mat) <= 2 * (gapo + gape), gapo >= 1, gape > 0, max(mat) * min(qlen, tlen) < 32000 and
+ *                        gapo + gape < 16000), a job with qlen or tlen above max_len, and an empty job;
+ *   MM2AMD_LL_PATH_WG    ksw_ll_kernel, one workgroup of wg_waves wavefronts per job: qlen > strip_cols and qlen * tlen >= wg_min_cells;
+ *   MM2AMD_LL_PATH_WAVE  ksw_ll_kernel, one wavefront per job: every other job.
+ * An empty job (qlen == 0 or tlen == 0) gives score 0 and qe = te = -1 (the reference reads outside its arrays there).  Results are in job
+ * order.  MM2AMD_EINVAL for m != 5, a null argument, a negative length or a code above 4; n_jobs == 0 returns 0; like every compute entry point
+ * the call needs a device (MM2AMD_ENODEV), also when the host would compute every job.  Device buffers are kept between calls.
+ * mm2amd_ksw_ll_limits reports strip_cols, wg_waves, wg_min_cells (as in force, see below) and max_len (65535); any pointer may be NULL.
+ * Two environment variables are read at every call: MM2AMD_LL_NO_WG=1 sends every device job through the wave class (the A/B of
+ * tools/ksw_ll_bench.py); MM2AMD_LL_WG_MIN_CELLS=<n> replaces wg_min_cells (tests send tiny jobs through the workgroup class with it). */
+#define MM2AMD_LL_QREV  1
+#define MM2AMD_LL_QCOMP 2
+#define MM2AMD_LL_TREV  4
+#define MM2AMD_LL_PATH_WAVE 0
+#define MM2AMD_LL_PATH_WG   1
+#define MM2AMD_LL_PATH_HOST 2
+typedef struct { const uint8_t *query, *target; int32_t qlen, tlen; int32_t flag; } mm2amd_ll_job_t;
+typedef struct { int32_t score, qe, te, path; } mm2amd_ll_res_t;
+int mm2amd_ksw_ll_batch(int n_jobs, const mm2amd_ll_job_t *jobs, int8_t m, const int8_t *mat, int gapo, int gape, mm2amd_ll_res_t *res);
+int mm2amd_ksw_ll_limits(int *strip_cols, int *wg_waves, int64_t *wg_min_cells, int *max_len);
+
 /* The two device-wide primitives of the index build (device_sort.hip), exposed for testing.  mm2amd_sort_pairs_u64: n (key, value) pairs
  * sorted in place by key bits [0, bits), stably -- what radix_sort_128x (ksort.h:101-151, instantiated at sketch.c:13 and called per bucket
  * at index.c:236) yields for pairs whose input order is ascending in the value: rs_hist / rs_chunk_scan / rs_block_offsets / rs_scatter

@@ -42,6 +42,14 @@ class TxtRes(C.Structure):  # mm2amd_txt_res_t
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("status", C.c_int32)]
 
 
+class LlJob(C.Structure):  # mm2amd_ll_job_t
+    _fields_ = [("query", C.c_void_p), ("target", C.c_void_p), ("qlen", C.c_int32), ("tlen", C.c_int32), ("flag", C.c_int32)]
+
+
+class LlRes(C.Structure):  # mm2amd_ll_res_t
+    _fields_ = [("score", C.c_int32), ("qe", C.c_int32), ("te", C.c_int32), ("path", C.c_int32)]
+
+
 class KswRes(C.Structure):  # mm2amd_ksw_res_t
     _fields_ = [(n, C.c_int32) for n in ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score",
                                          "n_cigar", "reach_end")] + [("cigar_off", C.c_uint32)]
@@ -104,6 +112,8 @@ I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
 EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
 DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
 TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD = 0, 1, 2, 3  # MM2AMD_TXT_*
+LL_QREV, LL_QCOMP, LL_TREV = 1, 2, 4  # MM2AMD_LL_*
+LL_PATH_WAVE, LL_PATH_WG, LL_PATH_HOST = 0, 1, 2  # MM2AMD_LL_PATH_*
 
 _lib = None
 
@@ -143,6 +153,9 @@ def _bind(L):
         L.mm2amd_hits_text_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(TxtRes), vp,
                                              C.c_size_t]
         L.mm2amd_idx_getseq.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        if hasattr(L, "mm2amd_ksw_ll_batch"):
+            L.mm2amd_ksw_ll_batch.argtypes = [C.c_int, C.POINTER(LlJob), C.c_int8, C.c_char_p, C.c_int, C.c_int, C.POINTER(LlRes)]
+            L.mm2amd_ksw_ll_limits.argtypes = [ip, ip, C.POINTER(C.c_int64), ip]
         L.mm2amd_sort_pairs_u64.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mm2amd_exclusive_sum_u32.argtypes = [vp, vp, C.c_uint64]
         L.mm2amd_idx_str.restype = vp
@@ -338,6 +351,30 @@ def aln_text_batch(jobs, what):
         arr[i].qlen, arr[i].tlen, arr[i].cigar, arr[i].n_cigar = len(qb or b""), len(tb or b""), ca, len(cig)
     L = lib()
     return _texts(lambda res, pool, cap: L.mm2amd_aln_text_batch(n, arr, what, res, pool, cap), n)
+
+
+def ksw_ll_batch(jobs, mat, gapo, gape):
+    """jobs: list of (query_codes, target_codes) or (query_codes, target_codes, flag) -- nt4 codes 0..4; flag: LL_QREV | LL_QCOMP | LL_TREV, how the
+    sequences are read.  Returns a list of (score, qe, te, path): what the reference's ksw_ll_qinit + ksw_ll_i16 (ksw2_ll_sse.c:37-152) return on
+    the sequences so transformed, and where the job ran (LL_PATH_WAVE / LL_PATH_WG: ksw_ll_kernel; LL_PATH_HOST: the host's scalar routine)."""
+    n = len(jobs)
+    arr = (LlJob * max(n, 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        qb, tb = bytes(j[0]), bytes(j[1])
+        keep.append((qb, tb))
+        arr[i].query, arr[i].target = C.cast(C.c_char_p(qb), C.c_void_p), C.cast(C.c_char_p(tb), C.c_void_p)
+        arr[i].qlen, arr[i].tlen, arr[i].flag = len(qb), len(tb), (j[2] if len(j) > 2 else 0)
+    res = (LlRes * max(n, 1))()
+    _check(lib().mm2amd_ksw_ll_batch(n, arr, 5, bytes(mat), gapo, gape, res))
+    return [(r.score, r.qe, r.te, r.path) for r in res[:n]]
+
+
+def ksw_ll_limits():
+    """mm2amd_ksw_ll_limits: the shapes behind ksw_ll_batch's routing -- strip_cols, wg_waves, wg_min_cells (as in force), max_len"""
+    a, b, d, c = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    _check(lib().mm2amd_ksw_ll_limits(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return {"strip_cols": a.value, "wg_waves": b.value, "wg_min_cells": c.value, "max_len": d.value}
 
 
 def hits_text(idx, hits, reads, what, is_qstrand=False):

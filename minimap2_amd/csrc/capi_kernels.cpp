@@ -10,6 +10,7 @@
 #include "kernel_prof.hpp"
 #include "region_finish.hpp"
 #include "aln_text.hpp"
+#include "ksw_ll.hpp"
 #include "device_sort.hpp"
 #include <map>
 
@@ -25,6 +26,21 @@ struct KernelApiState { // buffers of the kernel-level entry points
 	DevBuf<uint8_t> d_qpool, d_tpool;
 };
 KernelApiState &kstate() { static KernelApiState s; return s; }
+
+struct LlApiState { // mm2amd_ksw_ll_batch: kept between calls
+	DevBuf<uint8_t> d_q, d_t;
+	DevBuf<LlJob> d_jobs;
+	DevBuf<LlRes> d_res;
+	DevBuf<uint32_t> d_bnd;
+	PinBuf<uint8_t> h_q, h_t; // the pools are gathered in pinned memory: the uploads are then asynchronous copies in stream order
+	PinBuf<LlJob> h_jobs;
+	PinBuf<LlRes> h_res;
+};
+LlApiState &ll_state() { static LlApiState s; return s; }
+constexpr size_t kLlBndBudget = (size_t)1 << 26; // words of boundary columns per launch (256 MB): a batch that needs more is launched in parts
+
+bool ll_no_wg() { const char *e = getenv("MM2AMD_LL_NO_WG"); return e && *e && strcmp(e, "0") != 0; }
+int64_t ll_wg_min_cells() { const char *e = getenv("MM2AMD_LL_WG_MIN_CELLS"); return e && *e ? (int64_t)strtoll(e, nullptr, 10) : kLlWgMinCells; }
 
 template <typename F>
 int guarded(F &&f)
@@ -284,6 +300,119 @@ int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm
 		std::lock_guard<std::mutex> lk(dc.mu);
 		ensure_device(dc);
 		return aln_text_run(dc, tj, what, hq, ht, nullptr, cig, res, pool, pool_cap);
+	});
+}
+
+int mm2amd_ksw_ll_limits(int *strip_cols, int *wg_waves, int64_t *wg_min_cells, int *max_len)
+{
+	if (strip_cols) *strip_cols = kLlStrip;
+	if (wg_waves) *wg_waves = kLlWgWaves;
+	if (wg_min_cells) *wg_min_cells = ll_wg_min_cells();
+	if (max_len) *max_len = kLlMaxLen;
+	return 0;
+}
+
+int mm2amd_ksw_ll_batch(int n_jobs, const mm2amd_ll_job_t *jobs, int8_t m, const int8_t *mat, int gapo, int gape, mm2amd_ll_res_t *res)
+{
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat || m != 5) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: bad arguments (m must be 5)");
+	if (n_jobs == 0) return 0;
+	for (int i = 0; i < n_jobs; ++i) {
+		const mm2amd_ll_job_t &j = jobs[i];
+		if (j.qlen < 0 || j.tlen < 0 || (j.qlen > 0 && !j.query) || (j.tlen > 0 && !j.target)) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: bad job (negative length or null sequence)");
+		uint8_t top = 0;
+		for (int32_t k = 0; k < j.qlen; ++k) top |= (uint8_t)(j.query[k] > 4);
+		for (int32_t k = 0; k < j.tlen; ++k) top |= (uint8_t)(j.target[k] > 4);
+		if (top) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: a sequence holds a code above 4");
+	}
+	return guarded([&]() -> int {
+		DeviceCtx &dc = device_ctx();
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		LlApiState &d = ll_state();
+		const bool no_wg = ll_no_wg();
+		const int64_t wg_min = ll_wg_min_cells();
+		// routing: HOST, or one of the two launch classes; each class longest job first, so that a launch's tail is short
+		std::vector<int> cls[2], host;
+		for (int i = 0; i < n_jobs; ++i) {
+			const mm2amd_ll_job_t &j = jobs[i];
+			const int64_t cells = (int64_t)j.qlen * j.tlen;
+			if (cells == 0 || j.qlen > kLlMaxLen || j.tlen > kLlMaxLen || !ll_plain_class(j.qlen, j.tlen, mat, gapo, gape)) host.push_back(i), res[i].path = MM2AMD_LL_PATH_HOST;
+			else if (!no_wg && j.qlen > kLlStrip && cells >= wg_min) cls[1].push_back(i), res[i].path = MM2AMD_LL_PATH_WG;
+			else cls[0].push_back(i), res[i].path = MM2AMD_LL_PATH_WAVE;
+		}
+		std::vector<LlJob> dj;
+		struct Launch { size_t first; int n, waves; double cells; };
+		std::vector<Launch> launches;
+		size_t qtot = 0, ttot = 0, bnd_max = 1;
+		for (int c = 0; c < 2; ++c) {
+			std::vector<int> &v = cls[c];
+			std::stable_sort(v.begin(), v.end(), [&](int a, int b) { return (int64_t)jobs[a].qlen * jobs[a].tlen > (int64_t)jobs[b].qlen * jobs[b].tlen; });
+			const int waves = c ? kLlWgWaves : 1;
+			size_t bnd = 0;
+			Launch cur{ dj.size(), 0, waves, 0.0 };
+			for (int i : v) {
+				const mm2amd_ll_job_t &j = jobs[i];
+				const size_t need = j.qlen > kLlStrip ? (size_t)waves * ll_bnd_words(j.tlen) : 0;
+				if (cur.n > 0 && bnd + need > kLlBndBudget) { launches.push_back(cur); cur = Launch{ dj.size(), 0, waves, 0.0 }; bnd = 0; }
+				LlJob o;
+				o.q_off = qtot, o.t_off = ttot, o.bnd_off = bnd, o.qlen = j.qlen, o.tlen = j.tlen, o.flag = (uint32_t)j.flag & 7u, o.out = (uint32_t)i;
+				dj.push_back(o);
+				qtot += (size_t)j.qlen, ttot += (size_t)j.tlen, bnd += need;
+				bnd_max = std::max(bnd_max, bnd);
+				++cur.n, cur.cells += (double)j.qlen * j.tlen;
+			}
+			if (cur.n > 0) launches.push_back(cur);
+		}
+		if (!dj.empty()) {
+			uint8_t *const hq = d.h_q.ensure(qtot + 1), *const ht = d.h_t.ensure(ttot + 1);
+			LlJob *const hj = d.h_jobs.ensure(dj.size());
+			d.h_res.ensure((size_t)n_jobs);
+			for (size_t k = 0; k < dj.size(); ++k) {
+				const LlJob &o = dj[k];
+				memcpy(hq + o.q_off, jobs[o.out].query, (size_t)o.qlen);
+				memcpy(ht + o.t_off, jobs[o.out].target, (size_t)o.tlen);
+				hj[k] = o;
+			}
+			d.d_q.ensure(qtot + 1), d.d_t.ensure(ttot + 1), d.d_jobs.ensure(dj.size()), d.d_res.ensure((size_t)n_jobs), d.d_bnd.ensure(bnd_max);
+			HIP_CHECK(hipMemcpyAsync(d.d_q.p, hq, qtot + 1, hipMemcpyHostToDevice, dc.stream));
+			HIP_CHECK(hipMemcpyAsync(d.d_t.p, ht, ttot + 1, hipMemcpyHostToDevice, dc.stream));
+			HIP_CHECK(hipMemcpyAsync(d.d_jobs.p, hj, dj.size() * sizeof(LlJob), hipMemcpyHostToDevice, dc.stream));
+			LlParams P;
+			P.qpool = d.d_q.p, P.tpool = d.d_t.p, P.bnd = d.d_bnd.p, P.res = d.d_res.p, P.goe = gapo + gape, P.ge = gape;
+			for (int qc = 0; qc < 5; ++qc) { // ksw_ll_qinit's profile: target code a against query code qc scores mat[a * m + qc] (ksw2_ll_sse.c:63-71)
+				P.sc_lo[qc] = 0;
+				for (int a = 0; a < 4; ++a) P.sc_lo[qc] |= (uint32_t)(uint8_t)mat[a * 5 + qc] << (8 * a);
+				P.sc_hi[qc] = mat[20 + qc];
+			}
+			KernelProfiler &prof = kernel_profiler(0);
+			for (const Launch &l : launches) {
+				P.jobs = d.d_jobs.p + l.first, P.n_jobs = l.n, P.n_waves = l.waves;
+				prof.begin(dc.stream);
+				ksw_ll_launch(P, dc.stream);
+				prof.end(dc.stream, l.waves == 1 ? "ksw_ll_kernel[wave]" : "ksw_ll_kernel[wg]", 0.0, l.cells);
+			}
+		}
+		// the host's share while the device works: the sequences as the flags say, then the scalar routine
+		std::vector<uint8_t> hq1, ht1;
+		for (int i : host) {
+			const mm2amd_ll_job_t &j = jobs[i];
+			if (j.qlen == 0 || j.tlen == 0) { res[i].score = 0, res[i].qe = res[i].te = -1; continue; } // (nothing to align: the contract's answer)
+			hq1.assign(j.query, j.query + j.qlen), ht1.assign(j.target, j.target + j.tlen);
+			if (j.flag & MM2AMD_LL_QREV) std::reverse(hq1.begin(), hq1.end());
+			if (j.flag & MM2AMD_LL_QCOMP) for (uint8_t &c : hq1) c = c < 4 ? 3 - c : 4;
+			if (j.flag & MM2AMD_LL_TREV) std::reverse(ht1.begin(), ht1.end());
+			int qe = -1, te = -1;
+			res[i].score = ll_local_score(j.qlen, hq1.data(), j.tlen, ht1.data(), mat, gapo, gape, &qe, &te);
+			res[i].qe = qe, res[i].te = te;
+		}
+		if (!dj.empty()) {
+			const LlRes *const hr = d.h_res.p;
+			HIP_CHECK(hipMemcpyAsync(d.h_res.p, d.d_res.p, (size_t)n_jobs * sizeof(LlRes), hipMemcpyDeviceToHost, dc.stream));
+			HIP_CHECK(hipStreamSynchronize(dc.stream));
+			kernel_profiler(0).collect();
+			for (const LlJob &o : dj) res[o.out].score = hr[o.out].score, res[o.out].qe = hr[o.out].qe, res[o.out].te = hr[o.out].te;
+		}
+		return 0;
 	});
 }
 

@@ -2,13 +2,15 @@
 // ksw_ll_qinit + ksw_ll_i16 (ksw2_ll_sse.c:37-152).  The reference runs Farrar's striped algorithm on 8 x int16
 // lanes with saturating arithmetic; the end coordinates it reports depend on the striped scan order (the LAST row
 // reaching the maximum, and within that row the last striped slot holding it), so we keep the same data layout:
-// query position p lives in segment j = p % slen, lane l = p / slen.  This path is rare (only after a large
-// Z-drop) and tiny, so it stays a scalar host routine.
+// query position p lives in segment j = p % slen, lane l = p / slen.  This file is the host routine: the pipeline's
+// own callers (rare: only after a large Z-drop) and every job outside the plain class use it; ksw_ll_kernel (ksw_ll_dev.hpp, behind
+// mm2amd_ksw_ll_batch) computes the plain class on the device.  ksw_ll.hpp holds the predicate that separates the two.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "align.hpp"
+#include "ksw_ll.hpp"
 
 namespace mm2amd {
 
@@ -152,12 +154,8 @@ int ll_local_score(int qlen, const uint8_t *query, int tlen, const uint8_t *targ
 {
 	*qe = *te = -1;
 	if (qlen <= 0 || tlen <= 0) return ll_local_score_striped(qlen, query, tlen, target, mat, gapo, gape, qe, te);
-	int worst = 0, best = 0;
-	for (int k = 0; k < 25; ++k) worst = std::min<int>(worst, mat[k]), best = std::max<int>(best, mat[k]);
-	// the plain matrix is the striped routine's whenever opening a gap right after a gap of the other kind cannot beat a substitution, and nothing saturates
-	// (gapo >= 1: with a free gap opening the striped routine itself leaves the plain matrix -- tests/cpucheck/ksw_ll_test.cpp shows both -- and stays the only form)
-	const bool plain = -worst <= 2 * (gapo + gape) && gapo >= 1 && gape > 0 && (long)best * std::min(qlen, tlen) < 32000 && static_cast<unsigned>(gapo + gape) < 16000u;
-	if (!plain) return ll_local_score_striped(qlen, query, tlen, target, mat, gapo, gape, qe, te);
+	// outside the plain class (ksw_ll.hpp) the striped routine stays the only form
+	if (!ll_plain_class(qlen, tlen, mat, gapo, gape)) return ll_local_score_striped(qlen, query, tlen, target, mat, gapo, gape, qe, te);
 	std::vector<int16_t> row_max((size_t)tlen, 0), row((size_t)qlen, 0);
 	const size_t n_cells = (size_t)qlen * (size_t)tlen;
 	std::vector<int16_t> all(n_cells <= ((size_t)24 << 20) ? n_cells : 0); // up to 48 MB: one sweep that keeps every score; beyond that a second sweep recomputes the row
