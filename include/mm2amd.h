@@ -305,6 +305,21 @@ int mm_gpu_format_batch(int n_frag, const int *seg_off, const int *n_seg, MM2AMD
  * than the formatting. */
 int mm_gpu_format_batch_view(int n_frag, const int *seg_off, const int *n_seg, MM2AMD_BSEQ_PTR seq, const int *n_reg, void *const *reg,
                              const int *rep_len, const char **out, size_t *out_len);
+/* The same text, byte for byte, with the records written on the device: one kernel (rec_text_kernel, one wavefront per record) writes what
+ * mm_write_paf4 (format.c:425-458) and mm_write_sam3 (format.c:522-679) write for single-segment reads -- the fixed fields, the CIGAR with the
+ * clips of write_sam_cigar (format.c:494-520), the tag block of write_tags (format.c:397-423), SA:Z: (format.c:638-664), cs (short and long) and
+ * MD (format.c:171-254, :302-331) -- except SEQ and QUAL of a SAM record, which are copies of host bytes and are put in place by the host pool.
+ * *out is a buffer the library owns, valid until the next mm_gpu_format_batch_dev call (or mm_gpu_destroy); the index and flags are the live
+ * context's; with several replicas the first one's device does the work; the call may run beside mm_gpu_map_staged.  *path says who wrote the
+ * text.  The whole batch goes to the host writer (MM2AMD_FMT_PATH_HOST -- still the right bytes) when a fragment has n_seg != 1, MM_F_OUT_DS is
+ * set, MM_F_COPY_COMMENT is set and a comment is present, a record's CIGAR has to go into the CG:B:I tag (MM_F_LONG_CIGAR, more than 65535
+ * operations), a de / dv value lies outside [0, 1], or cs / MD is asked of an index without sequence.  Everything else, an empty batch
+ * included, is written by the device.  MM2AMD_DEVICE_TEXT=1 in the environment routes mm_gpu_format_batch and mm_gpu_format_batch_view
+ * through the same path (unset or 0: the host writer, as ever). */
+#define MM2AMD_FMT_PATH_DEVICE 0
+#define MM2AMD_FMT_PATH_HOST   1
+int mm_gpu_format_batch_dev(int n_frag, const int *seg_off, const int *n_seg, MM2AMD_BSEQ_PTR seq, const int *n_reg, void *const *reg,
+                            const int *rep_len, const char **out, size_t *out_len, int *path);
 
 /* free() every reg[i][j].p and reg[i] (what the reference's step 2 does, map.c:629-631); for non-C callers. */
 void mm2amd_free_regs(int n_frag, int *n_reg, MM2AMD_REG_PP reg);

@@ -112,6 +112,7 @@ I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
 EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
 DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
 TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD = 0, 1, 2, 3  # MM2AMD_TXT_*
+FMT_PATH_DEVICE, FMT_PATH_HOST = 0, 1  # MM2AMD_FMT_PATH_*: who wrote the text of mm_gpu_format_batch_dev
 LL_QREV, LL_QCOMP, LL_TREV = 1, 2, 4  # MM2AMD_LL_*
 LL_PATH_WAVE, LL_PATH_WG, LL_PATH_HOST = 0, 1, 2  # MM2AMD_LL_PATH_*
 
@@ -183,6 +184,7 @@ def _bind(L):
         L.mm2amd_mapopt_init.argtypes = [vp]
         L.mm_gpu_format_batch.argtypes = [C.c_int, ip, ip, vp, ip, C.POINTER(vp), ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.mm_gpu_format_batch_view.argtypes = [C.c_int, ip, ip, vp, ip, C.POINTER(vp), ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.mm_gpu_format_batch_dev.argtypes = [C.c_int, ip, ip, vp, ip, C.POINTER(vp), ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), ip]
         L.mm2amd_profile_enable.argtypes = [C.c_int]
         L.mm2amd_profile_enable.restype = None
         L.mm2amd_profile_get.argtypes = [C.POINTER(KernelStat), C.c_int]
@@ -543,16 +545,17 @@ class Aligner(object):
     seq: a sequence string/bytes or a list of them (the reference); names: optional list of contig names.
     fn_idx_in: instead of seq, a file -- a minimap2 index (.mmi, read by mm2amd_idx_load; part: which part of a multi-part file, required when
     there is more than one; the file's k, w and flags replace the preset's) or FASTA / FASTQ, plain or gzip.  fn_idx_out: write the index there
-    as a .mmi (mm2amd_idx_dump) once it is built.
+    as a .mmi (mm2amd_idx_dump) once it is built.  extra_flags: MM_F_* bits ORed into map_opt.flag (mappy's parameter of the same name).
     n_gpus / device_ids: map every batch on several GPUs of this process (mm_gpu_init_index_multi: index replicated, reads sharded
     by bases; an ordinal may repeat).  Only one Aligner can be the active mapper of the process at a time (the drop-in boundary is
     a process-wide context, like the reference's pipeline): creating a second one makes the first inactive -- its map calls raise,
     and closing or collecting it leaves the new context alone."""
 
     def __init__(self, seq=None, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None,
-                 fn_idx_in=None, fn_idx_out=None, part=None):
+                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0):
         L = lib()
         self._generation, self._idx, self._staged = 0, None, None  # close() must work on a half-built object
+        self.last_format_path = None  # FMT_PATH_* of the last format_raw(device=True)
         if (seq is None) == (fn_idx_in is None):
             raise Mm2AmdError("give exactly one of seq and fn_idx_in")
         self.idx_opt, self.map_opt = IdxOpt(), MapOpt()
@@ -567,6 +570,7 @@ class Aligner(object):
             self.map_opt.flag |= F_CIGAR
         if sam:
             self.map_opt.flag |= F_OUT_SAM | F_CIGAR
+        self.map_opt.flag |= extra_flags  # MM_F_* bits beyond the preset's (mappy.Aligner's extra_flags)
         from_index = fn_idx_in is not None and idx_is_idx(fn_idx_in)
         if from_index:
             # a prebuilt index: its k, w and flag win over the preset's, as in the reference's reader (mm_idx_reader_read, index.c:621-635)
@@ -784,11 +788,18 @@ class Aligner(object):
     def free_raw(self, n_reg, reg):
         lib().mm2amd_free_regs(len(n_reg), n_reg, reg)
 
-    def format_raw(self, n_reg, reg, rep_len=None):
+    def format_raw(self, n_reg, reg, rep_len=None, device=False):
         """SAM (or PAF, by the aligner's options) records of the staged batch's raw results, as bytes: what the reference's
-        output step writes for these reads (mm_gpu_format_batch)."""
+        output step writes for these reads (mm_gpu_format_batch).  device=True: the records are written on the device
+        (mm_gpu_format_batch_dev); last_format_path then says who wrote them (FMT_PATH_DEVICE, or FMT_PATH_HOST for a batch the
+        device path leaves to the host writer)."""
         n, arr, _, seg_off, n_seg = self._staged
         out, out_len = C.c_void_p(), C.c_size_t()
+        if device:
+            path = C.c_int(-1)
+            _check(lib().mm_gpu_format_batch_dev(n, seg_off, n_seg, arr, n_reg, reg, rep_len, C.byref(out), C.byref(out_len), C.byref(path)))
+            self.last_format_path = path.value
+            return C.string_at(out, out_len.value)  # (the library owns the buffer)
         _check(lib().mm_gpu_format_batch(n, seg_off, n_seg, arr, n_reg, reg, rep_len, C.byref(out), C.byref(out_len)))
         try:
             return C.string_at(out, out_len.value)

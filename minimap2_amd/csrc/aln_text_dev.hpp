@@ -111,93 +111,98 @@ __device__ __forceinline__ void txt_copy_out(const uint32_t *stage, uint32_t a, 
 	}
 }
 
-} // namespace
-
+// Where a walk's text goes: the bytes so far, and one step's way from per-lane counts to the destination.  place(): every lane has counted its
+// bytes; offsets by a wave scan.  flush(): the writing pass has stored into the stage at `a` + its offset and the wave copies the step out.
 template <bool WRITE>
-__global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
-{
-	__shared__ uint32_t s_word[kTxtTileOps], s_q[kTxtTileOps], s_t[kTxtTileOps], s_col[kTxtTileOps];
-	__shared__ uint32_t s_stage[(64 * kTxtColBytes + 4 + 3) / 4 + 1];
-	const int lane = (int)threadIdx.x;
-	const int id = (int)blockIdx.x;
-	const TxtJob J = P.jobs[id];
-	const int what = P.what;
-	const uint32_t n = J.n_cigar;
-	const uint32_t *cg = P.cigar + J.cig_off;
-	const bool md = what == kTxtMd;
-
-	if (WRITE) { // the sizing pass has judged the job
-		const TxtRes r = P.res[id];
-		if (r.status != 0 || r.len == 0) return;
-	} else {
-		bool bad = false;
-		unsigned long long sq = 0, st = 0;
-		for (uint32_t k = (uint32_t)lane; k < n; k += 64u) {
-			const uint32_t w = cg[k], op = w & 0xf, len = w >> 4;
-			if (what == kTxtCigar) { bad |= op > 9u; continue; }
-			bad |= !(op <= 3u || op == 7u || op == 8u) || len == 0u || (op == 3u && len < 2u);
-			if (op == 0u || op == 7u || op == 8u) sq += len, st += len;
-			else if (op == 1u) sq += len;
-			else if (op == 2u || op == 3u) st += len;
-		}
-		if (what != kTxtCigar) {
-#pragma unroll
-			for (int d = 32; d > 0; d >>= 1) sq += __shfl_xor(sq, d, 64), st += __shfl_xor(st, d, 64);
-			bad |= J.qlen < 0 || J.tlen < 0 || sq != (unsigned long long)(long long)J.qlen || st != (unsigned long long)(long long)J.tlen;
-		}
-		if (__ballot(bad) != 0ull) { // (an invalid job writes nothing but its own result)
-			if (lane == 0) { TxtRes r; r.cols = 0, r.len = 0, r.status = -1; P.res[id] = r; }
-			return;
-		}
-	}
-
-	unsigned long long nbytes = 0; // text so far (the same in every lane)
-	char *const out = WRITE ? P.out + P.off[id] : nullptr;
-	// one step's text: every lane has counted its bytes; offsets by a wave scan; the writing pass stages and copies out
-	auto place = [&](uint32_t mine, uint32_t &a, uint32_t &excl) -> uint32_t {
+struct TxtOut {
+	char *out;                 // WRITE: where the text starts
+	uint32_t *stage;           // LDS, (64 * kTxtColBytes + 4 + 3) / 4 + 1 words
+	int lane;
+	unsigned long long nbytes; // text so far (the same in every lane)
+	__device__ __forceinline__ uint32_t place(uint32_t mine, uint32_t &a, uint32_t &excl) const
+	{
 		const uint32_t incl = wave_inclusive_sum(mine, lane);
 		excl = incl - mine;
 		a = WRITE ? (uint32_t)((uintptr_t)(out + nbytes) & 3u) : 0u;
 		return (uint32_t)__shfl((int)incl, 63, 64);
-	};
-	auto flush = [&](uint32_t a, uint32_t tot) {
+	}
+	__device__ __forceinline__ void flush(uint32_t a, uint32_t tot)
+	{
 		if (WRITE) {
 			TXT_SYNC();
-			txt_copy_out(s_stage, a, tot, out + nbytes, lane);
+			txt_copy_out(stage, a, tot, out + nbytes, lane);
 			TXT_SYNC();
 		}
 		nbytes += tot;
-	};
-
-	if (what == kTxtCigar) {
-		for (uint32_t k0 = 0; k0 < n; k0 += 64u) {
-			const uint32_t k = k0 + (uint32_t)lane;
-			const uint32_t w = k < n ? cg[k] : 0u;
-			TxtCount cnt;
-			if (k < n) txt_emit_cigar(cnt, w);
-			uint32_t a, excl;
-			const uint32_t tot = place(cnt.n, a, excl);
-			if (WRITE && k < n) { TxtStore s; s.p = (char *)s_stage + a + excl; txt_emit_cigar(s, w); }
-			flush(a, tot);
-		}
-		if (!WRITE && lane == 0) { TxtRes r; r.cols = n, r.len = (uint32_t)nbytes, r.status = nbytes > 0xffffffffull ? -1 : 0; if (r.status) r.len = 0; P.res[id] = r; }
-		return;
 	}
+};
 
-	const uint32_t qlen = (uint32_t)J.qlen, tlen = (uint32_t)J.tlen;
-	auto qbase = [&](uint32_t i) -> int {
-		if (J.qsrc == kTxtQCodes) { const int c = P.qpool[J.q_pos + i]; return c > 4 ? 4 : c; }
-		if (J.qsrc == kTxtQAscii) return txt_nt4(P.qpool[J.q_pos + i]);
-		const int c = txt_nt4(P.qpool[J.q_pos + (qlen - 1u - i)]);
+// The sizing pass's judgement of a CIGAR (64-bit sums: lengths that wrap must not pass for a CIGAR that covers the sequences); the same in every lane.
+__device__ __forceinline__ bool txt_bad_ops(const uint32_t *cg, uint32_t n, int what, int32_t qlen, int32_t tlen, int lane)
+{
+	bool bad = false;
+	unsigned long long sq = 0, st = 0;
+	for (uint32_t k = (uint32_t)lane; k < n; k += 64u) {
+		const uint32_t w = cg[k], op = w & 0xf, len = w >> 4;
+		if (what == kTxtCigar) { bad |= op > 9u; continue; }
+		bad |= !(op <= 3u || op == 7u || op == 8u) || len == 0u || (op == 3u && len < 2u);
+		if (op == 0u || op == 7u || op == 8u) sq += len, st += len;
+		else if (op == 1u) sq += len;
+		else if (op == 2u || op == 3u) st += len;
+	}
+	if (what != kTxtCigar) {
+#pragma unroll
+		for (int d = 32; d > 0; d >>= 1) sq += __shfl_xor(sq, d, 64), st += __shfl_xor(st, d, 64);
+		bad |= qlen < 0 || tlen < 0 || sq != (unsigned long long)(long long)qlen || st != (unsigned long long)(long long)tlen;
+	}
+	return __ballot(bad) != 0ull;
+}
+
+// "<len><op>" of every operation, 64 operations a step
+template <bool WRITE>
+__device__ __forceinline__ void txt_walk_cigar(TxtOut<WRITE> &O, const uint32_t *cg, uint32_t n)
+{
+	const int lane = O.lane;
+	for (uint32_t k0 = 0; k0 < n; k0 += 64u) {
+		const uint32_t k = k0 + (uint32_t)lane;
+		const uint32_t w = k < n ? cg[k] : 0u;
+		TxtCount cnt;
+		if (k < n) txt_emit_cigar(cnt, w);
+		uint32_t a, excl;
+		const uint32_t tot = O.place(cnt.n, a, excl);
+		if (WRITE && k < n) { TxtStore s; s.p = (char *)O.stage + a + excl; txt_emit_cigar(s, w); }
+		O.flush(a, tot);
+	}
+}
+
+struct TxtSeqs { // where the bases of a walk come from (aln_text.hpp: kTxtQ* / kTxtT*)
+	const uint8_t *qpool, *tpool;
+	const uint32_t *S;
+	uint64_t q_pos, t_pos;
+	uint32_t qlen, tlen, qsrc, tsrc;
+	__device__ __forceinline__ int qbase(uint32_t i) const
+	{
+		if (qsrc == kTxtQCodes) { const int c = qpool[q_pos + i]; return c > 4 ? 4 : c; }
+		if (qsrc == kTxtQAscii) return txt_nt4(qpool[q_pos + i]);
+		const int c = txt_nt4(qpool[q_pos + (qlen - 1u - i)]);
 		return c >= 4 ? 4 : 3 - c;
-	};
-	auto tbase = [&](uint32_t i) -> int {
-		if (J.tsrc == kTxtTCodes) { const int c = P.tpool[J.t_pos + i]; return c > 4 ? 4 : c; }
-		const uint64_t o = J.t_pos + (J.tsrc == kTxtTPacked ? i : tlen - 1u - i);
-		const int c = (int)(P.S[o >> 3] >> ((o & 7) << 2) & 0xf);
-		return J.tsrc == kTxtTPacked ? (c > 4 ? 4 : c) : (c < 4 ? 3 - c : 4);
-	};
+	}
+	__device__ __forceinline__ int tbase(uint32_t i) const
+	{
+		if (tsrc == kTxtTCodes) { const int c = tpool[t_pos + i]; return c > 4 ? 4 : c; }
+		const uint64_t o = t_pos + (tsrc == kTxtTPacked ? i : tlen - 1u - i);
+		const int c = (int)(S[o >> 3] >> ((o & 7) << 2) & 0xf);
+		return tsrc == kTxtTPacked ? (c > 4 ? 4 : c) : (c < 4 ? 3 - c : 4);
+	}
+};
 
+// cs (short or long) or MD of a CIGAR that txt_bad_ops has passed; s_word / s_q / s_t / s_col: kTxtTileOps words of LDS each.  Returns the columns walked.
+template <bool WRITE>
+__device__ __forceinline__ uint32_t txt_walk_columns(TxtOut<WRITE> &O, const TxtSeqs &Q, int what, const uint32_t *cg, uint32_t n,
+                                                     uint32_t *s_word, uint32_t *s_q, uint32_t *s_t, uint32_t *s_col)
+{
+	const int lane = O.lane;
+	const bool md = what == kTxtMd;
 	uint32_t cq = 0, ct = 0, ccol = 0; // what the operations staged so far consume: query, target, columns
 	uint32_t run_from = 0;             // the column the pending identity run starts at (max over the columns walked so far)
 	// one step: the lane's column c (or none) -> its text
@@ -210,13 +215,13 @@ __global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
 			while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (s_col[mid] <= c) lo = mid; else hi = mid; }
 			const uint32_t w = s_word[lo], op = w & 0xf, j = c - s_col[lo];
 			k.first = j == 0u;
-			if (op == 1u) k.kind = TXT_I, k.a = qbase(s_q[lo] + j);
-			else if (op == 2u) k.kind = TXT_D, k.b = tbase(s_t[lo] + j);
+			if (op == 1u) k.kind = TXT_I, k.a = Q.qbase(s_q[lo] + j);
+			else if (op == 2u) k.kind = TXT_D, k.b = Q.tbase(s_t[lo] + j);
 			else if (op == 3u) {
 				const uint32_t t0 = s_t[lo];
 				k.kind = TXT_N, k.len = w >> 4;
-				k.a = tbase(t0), k.b = tbase(t0 + 1u), k.c = tbase(t0 + k.len - 2u), k.d = tbase(t0 + k.len - 1u);
-			} else k.kind = TXT_M, k.a = qbase(s_q[lo] + j), k.b = tbase(s_t[lo] + j), k.ident = k.a == k.b;
+				k.a = Q.tbase(t0), k.b = Q.tbase(t0 + 1u), k.c = Q.tbase(t0 + k.len - 2u), k.d = Q.tbase(t0 + k.len - 1u);
+			} else k.kind = TXT_M, k.a = Q.qbase(s_q[lo] + j), k.b = Q.tbase(s_t[lo] + j), k.ident = k.a == k.b;
 			if (md) next_run = k.ident ? 0u : c + 1u;          // a mismatch or a deleted base: the count starts again behind it
 			else next_run = !k.ident ? c + 1u : k.first ? c : 0u; // cs: ... and an operation's first column starts a run of its own
 		}
@@ -230,9 +235,9 @@ __global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
 		TxtCount cnt;
 		txt_emit_column(cnt, k, what);
 		uint32_t a, excl;
-		const uint32_t tot = place(cnt.n, a, excl);
-		if (WRITE && cnt.n) { TxtStore s; s.p = (char *)s_stage + a + excl; txt_emit_column(s, k, what); }
-		flush(a, tot);
+		const uint32_t tot = O.place(cnt.n, a, excl);
+		if (WRITE && cnt.n) { TxtStore s; s.p = (char *)O.stage + a + excl; txt_emit_column(s, k, what); }
+		O.flush(a, tot);
 	};
 
 	for (uint32_t tile0 = 0; tile0 < n; tile0 += (uint32_t)kTxtTileOps) {
@@ -261,7 +266,41 @@ __global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
 		}
 	}
 	step(lane == 0, ccol, 0u, true); // the terminator
-	if (!WRITE && lane == 0) { TxtRes r; r.cols = ccol, r.len = (uint32_t)nbytes, r.status = nbytes > 0xffffffffull ? -1 : 0; if (r.status) r.len = 0; P.res[id] = r; }
+	return ccol;
+}
+
+} // namespace
+
+template <bool WRITE>
+__global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
+{
+	__shared__ uint32_t s_word[kTxtTileOps], s_q[kTxtTileOps], s_t[kTxtTileOps], s_col[kTxtTileOps];
+	__shared__ uint32_t s_stage[(64 * kTxtColBytes + 4 + 3) / 4 + 1];
+	const int lane = (int)threadIdx.x;
+	const int id = (int)blockIdx.x;
+	const TxtJob J = P.jobs[id];
+	const int what = P.what;
+	const uint32_t n = J.n_cigar;
+	const uint32_t *cg = P.cigar + J.cig_off;
+
+	if (WRITE) { // the sizing pass has judged the job
+		const TxtRes r = P.res[id];
+		if (r.status != 0 || r.len == 0) return;
+	} else if (txt_bad_ops(cg, n, what, J.qlen, J.tlen, lane)) { // (an invalid job writes nothing but its own result)
+		if (lane == 0) { TxtRes r; r.cols = 0, r.len = 0, r.status = -1; P.res[id] = r; }
+		return;
+	}
+
+	TxtOut<WRITE> O;
+	O.out = WRITE ? P.out + P.off[id] : nullptr, O.stage = s_stage, O.lane = lane, O.nbytes = 0;
+	uint32_t cols = n;
+	if (what == kTxtCigar) txt_walk_cigar(O, cg, n);
+	else {
+		TxtSeqs Q;
+		Q.qpool = P.qpool, Q.tpool = P.tpool, Q.S = P.S, Q.q_pos = J.q_pos, Q.t_pos = J.t_pos, Q.qlen = (uint32_t)J.qlen, Q.tlen = (uint32_t)J.tlen, Q.qsrc = J.qsrc, Q.tsrc = J.tsrc;
+		cols = txt_walk_columns(O, Q, what, cg, n, s_word, s_q, s_t, s_col);
+	}
+	if (!WRITE && lane == 0) { TxtRes r; r.cols = cols, r.len = (uint32_t)O.nbytes, r.status = O.nbytes > 0xffffffffull ? -1 : 0; if (r.status) r.len = 0; P.res[id] = r; }
 }
 
 void aln_text_launch(const TxtParams &P, bool write, void *stream)

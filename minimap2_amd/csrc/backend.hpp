@@ -9,6 +9,7 @@
 #include "ksw_dev.hpp"
 #include "region_finish.hpp"
 #include "region_dev.hpp"
+#include "rec_text.hpp"
 
 namespace mm2amd {
 
@@ -105,6 +106,17 @@ public:
 	// the chained anchors and minimizer positions of the listed reads of this lane's last seed_chain(.., lazy_chains) come to the host
 	// (one gather kernel, two copies); chains[i].a_p / mp_p point at them until the lane's next seed_chain()
 	virtual void fetch_chains(int /*lane*/, const std::vector<long> & /*reads*/, std::vector<ReadChains> & /*chains*/) {}
+	// The output stage on the device (rec_text.hpp), for the formatter's planner (format.cpp: format_batch_dev).  One call sequence at a time (the caller
+	// serialises them), and it may run beside every other member: it uses a stream and buffers of its own and only the immutable parts of the backend.
+	//   rec_text_begin   pinned buffers of the planned sizes, for the planner to fill;
+	//   rec_text_size    uploads them, runs the sizing pass; returns the records' results (pinned, valid until the next begin);
+	//   rec_text_write   the writing pass at the given offsets (one per record, host memory); returns the device's text (pinned, valid until the next begin).
+	struct RecTextSizes { size_t n_jobs = 0, n_hits = 0, name_bytes = 0, q_bytes = 0, cigar_words = 0; };
+	struct RecTextBufs { RecJob *jobs = nullptr; RecHit *hits = nullptr; char *names = nullptr; uint8_t *q = nullptr; uint32_t *cigar = nullptr; uint64_t *off = nullptr; };
+	virtual bool writes_records() const { return false; }
+	virtual RecTextBufs rec_text_begin(const RecTextSizes & /*sz*/) { return RecTextBufs(); }
+	virtual const RecRes *rec_text_size(int64_t /*flag*/) { return nullptr; }
+	virtual const char *rec_text_write(uint64_t /*total*/) { return nullptr; }
 	virtual bool finishes_regions() const { return false; }
 	virtual void finish_regions(int /*lane*/, const std::vector<FinRegion> & /*regions*/, const std::vector<FinPiece> & /*pieces*/, size_t /*out_words*/, const int8_t * /*mat25*/,
 	                            int /*q*/, int /*e*/, bool /*log_gap*/, std::vector<FinResult> & /*results*/, const uint32_t ** /*cigars*/) {}

@@ -106,7 +106,7 @@ public:
 		while ((1ull << rid_bits_) < fi.n_seq) ++rid_bits_;
 		n_lanes_ = 8; // sub-batches in flight.  Rounds 1-3: 5 (more made no difference while the lanes' waits spun on the CPU quota); with the lanes starting
 		              // on the next batch early, 8-10 keep seeding, sorting and DP kernels of different sub-batches on the GPU together: +3-4 % (profiles/r04, call 16)
-		if (const char *e = getenv("MM2AMD_LANES")) n_lanes_ = std::max(1, std::min(kMaxProfLanes, atoi(e)));
+		if (const char *e = getenv("MM2AMD_LANES")) n_lanes_ = std::max(1, std::min(kMaxProfLanes - 1, atoi(e))); // (the last profiler slot is the record formatter's)
 		for (int i = 0; i < n_lanes_; ++i) {
 			lanes_.emplace_back(new Lane);
 			lanes_.back()->id = i;
@@ -134,6 +134,7 @@ public:
 		(void)hipSetDevice(dev_);
 		if (stage_stream_) (void)hipStreamDestroy(stage_stream_);
 		for (int l = 0; l < n_lanes_; ++l) kernel_profiler(l, replica_).drop_events();
+		kernel_profiler(kMaxProfLanes - 1, replica_).drop_events(); // (the record formatter's slot)
 	}
 	int n_lanes() const override { return n_lanes_; }
 	void enable_name_rules() override
@@ -898,7 +899,100 @@ public:
 		prof.collect();
 	}
 
+	// ---- the output stage on the device (rec_text.hpp).  Its stream, buffers and profiler slot are its own; of the backend it reads the device's ordinal, the
+	// packed sequence's address and the index's name table, none of which changes after construction -- so it runs beside the lanes' mapping.
+	bool writes_records() const override { return true; }
+	RecTextBufs rec_text_begin(const RecTextSizes &sz) override
+	{
+		HIP_CHECK(hipSetDevice(dev_));
+		RecText &R = rt_;
+		if (!R.stream) HIP_CHECK(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
+		if (!R.targets_ready) { // target names and lengths: once per context, when the first batch is formatted here
+			const size_t n_seq = fi_seq_len_->size();
+			uint64_t tot = 0;
+			for (size_t i = 0; i < n_seq; ++i) tot += (*fi_names_)[i].size();
+			char *nm = R.h_tnames.ensure(tot + 1);
+			uint64_t *to = R.h_tname_off.ensure(n_seq + 1);
+			uint32_t *tl = R.h_tlen.ensure(n_seq + 1);
+			tot = 0;
+			for (size_t i = 0; i < n_seq; ++i) {
+				to[i] = tot, tl[i] = (*fi_seq_len_)[i];
+				memcpy(nm + tot, (*fi_names_)[i].data(), (*fi_names_)[i].size());
+				tot += (*fi_names_)[i].size();
+			}
+			to[n_seq] = tot;
+			R.d_tnames.ensure(tot + 1), R.d_tname_off.ensure(n_seq + 1), R.d_tlen.ensure(n_seq + 1);
+			if (tot) HIP_CHECK(hipMemcpyAsync(R.d_tnames.p, nm, tot, hipMemcpyHostToDevice, R.stream));
+			HIP_CHECK(hipMemcpyAsync(R.d_tname_off.p, to, (n_seq + 1) * 8, hipMemcpyHostToDevice, R.stream));
+			if (n_seq) HIP_CHECK(hipMemcpyAsync(R.d_tlen.p, tl, n_seq * 4, hipMemcpyHostToDevice, R.stream));
+			stream_wait(R.stream);
+			R.targets_ready = true;
+		}
+		R.sz = sz;
+		RecTextBufs b;
+		b.jobs = R.h_jobs.ensure(sz.n_jobs + 1), b.hits = R.h_hits.ensure(sz.n_hits + 1), b.names = R.h_names.ensure(sz.name_bytes + 1);
+		b.q = R.h_q.ensure(sz.q_bytes + 1), b.cigar = R.h_cigar.ensure(sz.cigar_words + 1), b.off = R.h_off.ensure(sz.n_jobs + 1);
+		R.h_res.ensure(sz.n_jobs + 1);
+		return b;
+	}
+	const RecRes *rec_text_size(int64_t flag) override
+	{
+		HIP_CHECK(hipSetDevice(dev_));
+		RecText &R = rt_;
+		const RecTextSizes &sz = R.sz;
+		if (sz.n_jobs == 0) return R.h_res.p;
+		R.d_jobs.ensure(sz.n_jobs), R.d_hits.ensure(sz.n_hits + 1), R.d_names.ensure(sz.name_bytes + 1), R.d_q.ensure(sz.q_bytes + 1), R.d_cigar.ensure(sz.cigar_words + 1);
+		R.d_res.ensure(sz.n_jobs), R.d_off.ensure(sz.n_jobs);
+		HIP_CHECK(hipMemcpyAsync(R.d_jobs.p, R.h_jobs.p, sz.n_jobs * sizeof(RecJob), hipMemcpyHostToDevice, R.stream));
+		if (sz.n_hits) HIP_CHECK(hipMemcpyAsync(R.d_hits.p, R.h_hits.p, sz.n_hits * sizeof(RecHit), hipMemcpyHostToDevice, R.stream));
+		if (sz.name_bytes) HIP_CHECK(hipMemcpyAsync(R.d_names.p, R.h_names.p, sz.name_bytes, hipMemcpyHostToDevice, R.stream));
+		if (sz.q_bytes) HIP_CHECK(hipMemcpyAsync(R.d_q.p, R.h_q.p, sz.q_bytes, hipMemcpyHostToDevice, R.stream));
+		if (sz.cigar_words) HIP_CHECK(hipMemcpyAsync(R.d_cigar.p, R.h_cigar.p, sz.cigar_words * 4, hipMemcpyHostToDevice, R.stream));
+		RecParams &P = R.P;
+		P.jobs = R.d_jobs.p, P.n_jobs = (int)sz.n_jobs, P.hits = R.d_hits.p, P.flag = flag, P.names = R.d_names.p, P.qpool = R.d_q.p, P.S = T_->S.p, P.cigar = R.d_cigar.p;
+		P.tnames = R.d_tnames.p, P.tname_off = R.d_tname_off.p, P.tlen = R.d_tlen.p, P.res = R.d_res.p, P.off = nullptr, P.out = nullptr;
+		KernelProfiler &prof = kernel_profiler(kMaxProfLanes - 1, replica_);
+		prof.begin(R.stream);
+		rec_text_launch(P, false, R.stream);
+		prof.end(R.stream, "rec_text_kernel[size]", (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
+		HIP_CHECK(hipMemcpyAsync(R.h_res.p, R.d_res.p, sz.n_jobs * sizeof(RecRes), hipMemcpyDeviceToHost, R.stream));
+		stream_wait(R.stream);
+		prof.collect();
+		return R.h_res.p;
+	}
+	const char *rec_text_write(uint64_t total) override
+	{
+		HIP_CHECK(hipSetDevice(dev_));
+		RecText &R = rt_;
+		const RecTextSizes &sz = R.sz;
+		R.h_out.ensure(total + 1);
+		if (sz.n_jobs == 0 || total == 0) return R.h_out.p;
+		R.d_out.ensure(total + 8);
+		HIP_CHECK(hipMemcpyAsync(R.d_off.p, R.h_off.p, sz.n_jobs * 8, hipMemcpyHostToDevice, R.stream));
+		R.P.off = R.d_off.p, R.P.out = R.d_out.p;
+		KernelProfiler &prof = kernel_profiler(kMaxProfLanes - 1, replica_);
+		prof.begin(R.stream);
+		rec_text_launch(R.P, true, R.stream);
+		prof.end(R.stream, "rec_text_kernel[write]", (double)total + (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
+		HIP_CHECK(hipMemcpyAsync(R.h_out.p, R.d_out.p, total, hipMemcpyDeviceToHost, R.stream));
+		stream_wait(R.stream);
+		prof.collect();
+		return R.h_out.p;
+	}
+
 private:
+	struct RecText {
+		hipStream_t stream = nullptr;
+		bool targets_ready = false;
+		RecTextSizes sz;
+		RecParams P{};
+		PinBuf<char> h_tnames; PinBuf<uint64_t> h_tname_off; PinBuf<uint32_t> h_tlen;
+		DevBuf<char> d_tnames; DevBuf<uint64_t> d_tname_off; DevBuf<uint32_t> d_tlen;
+		PinBuf<RecJob> h_jobs; PinBuf<RecHit> h_hits; PinBuf<char> h_names; PinBuf<uint8_t> h_q; PinBuf<uint32_t> h_cigar; PinBuf<uint64_t> h_off; PinBuf<RecRes> h_res; PinBuf<char> h_out;
+		DevBuf<RecJob> d_jobs; DevBuf<RecHit> d_hits; DevBuf<char> d_names; DevBuf<uint8_t> d_q; DevBuf<uint32_t> d_cigar; DevBuf<uint64_t> d_off; DevBuf<RecRes> d_res; DevBuf<char> d_out;
+		~RecText() { if (stream) (void)hipStreamDestroy(stream); }
+	};
+	RecText rt_;
 	// At most dp_gate_ lanes between the ordering of their DP batch and its last kernel (0: no limit).  The DP kernels are VALU-bound persistent launches: eight that
 	// coincide share the SIMDs round-robin and ALL finish late; admitted four at a time the first ones finish early and their lanes go on to consume, finish and the next
 	// sub-batch's seeding while the others compute.  Measured (calls 23-24, 8-step runs in one call each): no gate 2.24-2.28 Gbases/s with 47-52 ms per streaming

@@ -73,6 +73,8 @@ struct MapContext {
 	std::mutex stats_mu;
 	FormatScratch fmt;                // mm_gpu_format_batch_view's reusable text buffers
 	std::mutex fmt_mu;
+	FormatScratch fmt_dev;            // mm_gpu_format_batch_dev's
+	std::mutex fmt_dev_mu;            // one call at a time drives the first replica's record kernel (taken after fmt_mu where both are held)
 	int n_threads = 1;
 	uint64_t generation = 0;
 	const void *mi_ptr = nullptr;     // the reference index this context mirrors (mm_gpu_init; the batch-of-one calls compare it ...
@@ -187,6 +189,28 @@ int build_context(std::unique_ptr<MapContext> &c, void *device_tables, int table
 	for (Replica &rp : c->reps) c->stages_beside_mapping &= rp.mapper->stages_beside_mapping();
 	c->generation = ++g_generation;
 	return 0;
+}
+
+bool device_text_env() { const char *e = getenv("MM2AMD_DEVICE_TEXT"); return e && *e && strcmp(e, "0") != 0; } // A/B switch: the existing entry points take the device path
+
+// the batch's text through the first replica's record kernel (format_batch_dev) into `fs`; 0 or an MM2AMD_E* code (message set)
+int format_on_device(MapContext &c, const char *who, int n_threads, int n_frag, const int *seg_off, const int *n_seg, const void *seq_, const int *n_reg, void *const *reg,
+                     const int *rep_len, FormatScratch &fs, const char **out, size_t *out_len, int *path)
+{
+	std::lock_guard<std::mutex> lk(c.fmt_dev_mu);
+	try {
+		bool on_device = false;
+		*out = format_batch_dev(*c.reps.at(0).be, *c.fi, c.opt, n_threads, n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq_, n_reg, reg, rep_len, fs, out_len, &on_device);
+		if (!*out) return capi_fail(MM2AMD_ENOMEM, std::string("[mm2amd] ") + who + ": out of memory");
+		if (path) *path = on_device ? MM2AMD_FMT_PATH_DEVICE : MM2AMD_FMT_PATH_HOST;
+		return 0;
+	} catch (const std::bad_alloc &) {
+		return capi_fail(MM2AMD_ENOMEM, std::string("[mm2amd] ") + who + ": out of memory");
+	} catch (const std::invalid_argument &e) {
+		return capi_fail(MM2AMD_EINVAL, e.what());
+	} catch (const std::exception &e) {
+		return capi_fail(MM2AMD_EHIP, e.what());
+	}
 }
 
 uint64_t g_stamp_hash(const ref::Idx *mi) { return (uint64_t)mi->k | (uint64_t)mi->w << 8 | (uint64_t)(uint32_t)mi->flag << 16 | (uint64_t)mi->n_seq << 32; }
@@ -484,6 +508,13 @@ int mm_gpu_format_batch(int n_frag, const int *seg_off, const int *n_seg, const 
 		if (n_seg && n_seg[i] != 1 && n_seg[i] != 2) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm_gpu_format_batch: fragments of one or two segments only");
 	const std::string why = format_check(g_ctx->opt);
 	if (!why.empty()) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm_gpu_format_batch: " + why);
+	if (device_text_env()) { // the device's text, handed over as the malloc'd block this entry point promises
+		FormatScratch fs;
+		const char *text = nullptr;
+		if (int rc = format_on_device(*g_ctx, "mm_gpu_format_batch", g_ctx->n_threads, n_frag, seg_off, n_seg, seq_, n_reg, reg, rep_len, fs, &text, out_len, nullptr)) return rc;
+		*out = fs.buf, fs.buf = nullptr, fs.cap = 0;
+		return 0;
+	}
 	try {
 		*out = format_batch(*g_ctx->fi, g_ctx->opt, g_ctx->n_threads, n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq_, n_reg, reg, rep_len, out_len);
 		if (!*out) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] mm_gpu_format_batch: out of memory");
@@ -503,6 +534,7 @@ int mm_gpu_format_batch_view(int n_frag, const int *seg_off, const int *n_seg, c
 	const std::string why = format_check(g_ctx->opt);
 	if (!why.empty()) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm_gpu_format_batch_view: " + why);
 	std::lock_guard<std::mutex> lk_fmt(g_ctx->fmt_mu); // one formatting call at a time uses the buffers (pipeline step 2)
+	if (device_text_env()) return format_on_device(*g_ctx, "mm_gpu_format_batch_view", std::max(1, g_ctx->n_threads / 2), n_frag, seg_off, n_seg, seq_, n_reg, reg, rep_len, g_ctx->fmt, out, out_len, nullptr);
 	try {
 		// (this step runs beside the mapping of the next batch: half the threads)
 		*out = format_batch_view(*g_ctx->fi, g_ctx->opt, std::max(1, g_ctx->n_threads / 2), n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq_, n_reg, reg, rep_len, g_ctx->fmt, out_len);
@@ -511,6 +543,21 @@ int mm_gpu_format_batch_view(int n_frag, const int *seg_off, const int *n_seg, c
 	} catch (const std::exception &e) {
 		return capi_fail(MM2AMD_EINVAL, e.what());
 	}
+}
+
+// mm_gpu_format_batch_view's text with the records written by rec_text_kernel on the first replica's device (format.cpp: format_batch_dev)
+int mm_gpu_format_batch_dev(int n_frag, const int *seg_off, const int *n_seg, const void *seq_, const int *n_reg, void *const *reg, const int *rep_len, const char **out, size_t *out_len,
+                            int *path)
+{
+	std::shared_lock<std::shared_mutex> lk(g_ctx_mu);
+	if (!g_ctx) return capi_fail(MM2AMD_ESTATE, "[mm2amd] mm_gpu_format_batch_dev called before mm_gpu_init");
+	if (n_frag < 0 || !out || !out_len || !path || (n_frag > 0 && (!seq_ || !n_reg || !reg))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm_gpu_format_batch_dev: bad arguments");
+	for (int i = 0; i < n_frag; ++i)
+		if (n_seg && n_seg[i] != 1 && n_seg[i] != 2) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm_gpu_format_batch_dev: fragments of one or two segments only");
+	const std::string why = format_check(g_ctx->opt);
+	if (!why.empty()) return capi_fail(MM2AMD_EINVAL, "[mm2amd] mm_gpu_format_batch_dev: " + why);
+	// (this step runs beside the mapping of the next batch: half the threads)
+	return format_on_device(*g_ctx, "mm_gpu_format_batch_dev", std::max(1, g_ctx->n_threads / 2), n_frag, seg_off, n_seg, seq_, n_reg, reg, rep_len, g_ctx->fmt_dev, out, out_len, path);
 }
 
 void mm2amd_free_regs(int n_frag, int *n_reg, void **reg)

@@ -15,6 +15,9 @@
 #include <string>
 #include <vector>
 #include "format.hpp"
+#include "fraction.hpp"
+#include "backend.hpp"
+#include "aln_text.hpp"
 #include "threads.hpp"
 #include "host_prof.hpp"
 #if defined(__x86_64__)
@@ -132,26 +135,11 @@ double event_identity(const Text &o, const Reg1 &r) // mm_event_identity (align.
 	return (double)r.mlen / (r.blen + r.p->n_ambi - n_gap + n_gapo);
 }
 
-// "%.4f" of v in [0, 1] exactly as printf rounds it: the double is M x 2^-k, so v x 10^4 = M x 10^4 / 2^k is an exact 67-bit quotient and remainder -- round to
-// nearest, ties to even on the exact value (what glibc's printf does with its big-number arithmetic).  Anything else goes to snprintf.
+// "%.4f" of v in [0, 1] exactly as printf rounds it (fraction.hpp).  Anything else goes to snprintf.
 bool put_fraction_exact(Text &o, double v)
 {
 	if (!(v >= 0.0 && v <= 1.0)) return false;
-	uint64_t bits;
-	memcpy(&bits, &v, 8);
-	const int be = (int)(bits >> 52 & 0x7ff);
-	uint64_t M = bits & ((1ull << 52) - 1);
-	int k; // v = M x 2^-k
-	if (be == 0) k = 1074; else M |= 1ull << 52, k = 1075 - be;
-	unsigned q;
-	if (k <= 0) q = (unsigned)(M << -k) * 10000u; // (v == 1.0: M = 2^52, k = 52 -- never here; kept for completeness)
-	else if (k >= 120) q = 0; // below 2^-67: rounds to 0.0000
-	else {
-		const unsigned __int128 N = (unsigned __int128)M * 10000u, one = (unsigned __int128)1 << k;
-		const unsigned __int128 quo = N >> k, rem = N & (one - 1), half = one >> 1;
-		q = (unsigned)quo;
-		if (rem > half || (rem == half && (q & 1u))) ++q;
-	}
+	const unsigned q = fraction_q4(v); // fraction.hpp: the rounding rec_text_kernel uses as well
 	char *w = o.need(8);
 	w[0] = (char)('0' + q / 10000), w[1] = '.';
 	w[2] = (char)('0' + q / 1000 % 10), w[3] = (char)('0' + q / 100 % 10), w[4] = (char)('0' + q / 10 % 10), w[5] = (char)('0' + q % 10);
@@ -336,7 +324,7 @@ __attribute__((target("ssse3"))) static int revcomp_blocks(const char *seq, int 
 }
 #endif
 
-void put_seq(Text &o, const char *seq, int l, bool rev, bool comp) // sam_write_sq (format.c:470-482)
+void seq_into(char *w, const char *seq, int l, bool rev, bool comp) // sam_write_sq (format.c:470-482): l bytes at w
 {
 	static const std::array<char, 128> kComp = [] { // seq_comp_table (bseq.c:11-28) for ASCII: IUPAC complements, case preserved
 		std::array<char, 128> t;
@@ -345,8 +333,7 @@ void put_seq(Text &o, const char *seq, int l, bool rev, bool comp) // sam_write_
 		for (int i = 0; a[i]; ++i) t[(int)a[i]] = b[i];
 		return t;
 	}();
-	if (!rev) { o.str(seq, l); return; }
-	char *w = o.need((size_t)l);
+	if (!rev) { memcpy(w, seq, (size_t)l); return; }
 	if (comp) {
 		int i = 0;
 #if defined(__x86_64__)
@@ -355,6 +342,10 @@ void put_seq(Text &o, const char *seq, int l, bool rev, bool comp) // sam_write_
 		for (; i < l; ++i) { const int c = (unsigned char)seq[l - 1 - i]; w[i] = c < 128 ? kComp[c] : (char)c; }
 	}
 	else for (int i = 0; i < l; ++i) w[i] = seq[l - 1 - i];
+}
+void put_seq(Text &o, const char *seq, int l, bool rev, bool comp)
+{
+	seq_into(o.need((size_t)l), seq, l, rev, comp);
 	o.n += (size_t)l;
 }
 
@@ -601,6 +592,178 @@ const char *format_batch_view(const FlatIndex &fi, const MapOpt &opt, int n_thre
 		if (!fs.buf) { fs.cap = 0; return nullptr; }
 	}
 	parallel_for_side(n_threads, (long)off.size() - 1, [&](long c, int) { memcpy(fs.buf + off[c], fs.impl->parts[c].data(), fs.impl->parts[c].size()); }, 8);
+	fs.buf[total] = 0;
+	*out_len = total;
+	return fs.buf;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The same text with the records written on the device (rec_text.hpp).  The planner below decides which records a batch prints and in which
+// order (format_range's rules), fills one RecJob per record and one RecHit per hit, gathers the CIGARs, the read names and -- for cs / MD --
+// the reads' [qs, qe) letters into the backend's pinned buffers; the backend runs the sizing pass, the host turns the lengths into 64-bit
+// offsets, the backend runs the writing pass and brings the text back.  SEQ and QUAL of a SAM record are a hole in that text: the pool copies
+// every record's two pieces around put_seq's bytes into the final buffer.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct DevRec { int read, j; }; // a record: the read and its hit (-1: none)
+
+int sam_flag_of(const Reg1 *r) // mm_write_sam3's FLAG for a single-segment read
+{
+	if (!r) return 0x4;
+	int sf = r->rev ? 0x10 : 0;
+	if (r->parent != r->id) sf |= 0x100;
+	else if (!r->sam_pri) sf |= 0x800;
+	return sf;
+}
+// the hole of a SAM record, SEQ \t QUAL (format.c:617-634): 0 = whole read, 1 = "*\t*", 2 = [qs, qe)
+int hole_kind(const Reg1 *r, int64_t flag)
+{
+	const int sf = sam_flag_of(r);
+	if (!r || (sf & 0x900) == 0 || (flag & F_SOFTCLIP)) return 0;
+	return (sf & 0x100) && !(flag & F_SECONDARY_SEQ) ? 1 : 2;
+}
+size_t hole_len(const Bseq1 &t, const Reg1 *r, int64_t flag)
+{
+	const int k = hole_kind(r, flag);
+	if (k == 1) return 3;
+	const size_t l = k == 0 ? (size_t)t.l_seq : (size_t)(r->qe - r->qs);
+	return l + 1 + (t.qual ? l : 1);
+}
+char *hole_into(char *w, const Bseq1 &t, const Reg1 *r, int64_t flag)
+{
+	const int k = hole_kind(r, flag);
+	if (k == 1) { memcpy(w, "*\t*", 3); return w + 3; }
+	const bool rev = r && r->rev;
+	const int st = k == 0 ? 0 : r->qs, l = k == 0 ? t.l_seq : r->qe - r->qs;
+	seq_into(w, t.seq + st, l, rev, rev), w += l, *w++ = '\t';
+	if (t.qual) seq_into(w, t.qual + st, l, rev, false), w += l; else *w++ = '*';
+	return w;
+}
+
+} // namespace
+
+const char *format_batch_dev(Backend &be, const FlatIndex &fi, const MapOpt &opt, int n_threads, long n_frag, const int *seg_off, const int *n_seg, const Bseq1 *seq,
+                             const int *n_reg, void *const *reg, const int *rep_len, FormatScratch &fs, size_t *out_len, bool *on_device)
+{
+	const int64_t flag = opt.flag;
+	const bool sam = (flag & F_OUT_SAM) != 0, per_base = (flag & (F_OUT_CS | F_OUT_MD)) != 0, qstrand = (flag & F_QSTRAND) != 0;
+	auto host = [&]() { *on_device = false; return format_batch_view(fi, opt, n_threads, n_frag, seg_off, n_seg, seq, n_reg, reg, rep_len, fs, out_len); };
+	*on_device = true;
+	if (!be.writes_records() || (flag & F_OUT_DS)) return host();
+	if (per_base && ((fi.flag & ref::I_NO_SEQ) || !fi.S)) return host(); // cs / MD of an index without sequence
+	if (n_seg) for (long f = 0; f < n_frag; ++f) if (n_seg[f] != 1) return host();
+
+	// pass 1: the records, and where every read's share of the pools starts
+	struct ReadPlan { uint32_t hit0; uint64_t job0, name_off, cig_off, q_off; };
+	std::vector<ReadPlan> plan((size_t)n_frag);
+	std::vector<DevRec> recs;
+	Backend::RecTextSizes sz;
+	for (long f = 0; f < n_frag; ++f) {
+		const int i = seg_off ? seg_off[f] : (int)f;
+		const Bseq1 &t = seq[i];
+		const Reg1 *regs = (const Reg1 *)reg[i];
+		ReadPlan &pl = plan[f];
+		pl.hit0 = (uint32_t)sz.n_hits, pl.job0 = recs.size(), pl.name_off = sz.name_bytes, pl.cig_off = sz.cigar_words, pl.q_off = sz.q_bytes;
+		if ((flag & F_COPY_COMMENT) && t.comment) return host();
+		if (t.l_seq < 0 || !t.name || (t.l_seq > 0 && !t.seq)) return host();
+		if (n_reg[i] > 0) {
+			for (int j = 0; j < n_reg[i]; ++j) {
+				const Reg1 &r = regs[j];
+				// (what the kernel indexes with: a record the host writer would have to refuse as well goes to it)
+				if (r.rid < 0 || (uint32_t)r.rid >= fi.n_seq || r.rs < 0 || r.rs > r.re || (uint32_t)r.re > fi.seq_len[r.rid] || r.qs < 0 || r.qs > r.qe || r.qe > t.l_seq) return host();
+				if ((flag & F_NO_PRINT_2ND) && r.id != r.parent) continue;
+				if (sam && (flag & F_LONG_CIGAR) && r.p && r.p->n_cigar > 65535 - 2 && (int)r.p->n_cigar + (r.qs != 0) + (r.qe != t.l_seq) > 65535) return host(); // CG:B:I
+				recs.push_back(DevRec{ (int)f, j });
+				if (r.p) sz.cigar_words += r.p->n_cigar, sz.q_bytes += per_base ? (size_t)(r.qe - r.qs) : 0;
+			}
+			sz.n_hits += (size_t)n_reg[i];
+		} else if ((flag & F_PAF_NO_HIT) || (sam && !(flag & F_SAM_HIT_ONLY))) recs.push_back(DevRec{ (int)f, -1 });
+		if (recs.size() > pl.job0) sz.name_bytes += strlen(t.name);
+	}
+	sz.n_jobs = recs.size();
+	if (sz.n_jobs > 0x7fffffffull || sz.n_hits > 0x7fffffffull) return host();
+
+	// pass 2: the table and the pools, in the backend's pinned memory
+	const Backend::RecTextBufs B = be.rec_text_begin(sz);
+	const long chunk = 64, n_chunks = (n_frag + chunk - 1) / chunk;
+	parallel_for_side(n_threads, n_chunks, [&](long c, int) {
+		for (long f = c * chunk; f < std::min(n_frag, (c + 1) * chunk); ++f) {
+			const int i = seg_off ? seg_off[f] : (int)f;
+			const Bseq1 &t = seq[i];
+			const Reg1 *regs = (const Reg1 *)reg[i];
+			const ReadPlan &pl = plan[f];
+			const uint64_t job_end = f + 1 < n_frag ? plan[f + 1].job0 : recs.size();
+			if (job_end == pl.job0) continue;
+			const uint32_t name_len = (uint32_t)strlen(t.name);
+			memcpy(B.names + pl.name_off, t.name, name_len);
+			uint64_t cig = pl.cig_off, qo = pl.q_off;
+			const int n_hits = n_reg[i] > 0 ? n_reg[i] : 0;
+			uint64_t job = pl.job0;
+			for (int j = 0; j < n_hits; ++j) {
+				const Reg1 &r = regs[j];
+				RecHit &h = B.hits[pl.hit0 + j];
+				memset(&h, 0, sizeof h);
+				h.rid = r.rid, h.rs = r.rs, h.re = r.re, h.qs = r.qs, h.qe = r.qe, h.mlen = r.mlen, h.blen = r.blen, h.cnt = r.cnt, h.score = r.score, h.subsc = r.subsc, h.div = r.div;
+				h.bits = r.mapq | (uint32_t)r.split << kRecSplitShift | (r.rev ? kRecRev : 0u) | (r.inv ? kRecInv : 0u) | (r.sam_pri ? kRecSamPri : 0u) | (r.p ? kRecHasP : 0u) |
+				         (r.id == r.parent ? kRecIsParent : 0u);
+				if (r.p) h.dp_max0 = r.p->dp_max0, h.dp_score = r.p->dp_score, h.n_ambi = r.p->n_ambi, h.bits |= (uint32_t)r.p->trans_strand << kRecTransShift;
+				const bool printed = job < job_end && recs[job].j == j;
+				if (!printed) continue;
+				RecJob &J = B.jobs[job];
+				J.name_off = pl.name_off, J.name_len = name_len, J.l_seq = t.l_seq, J.rep_len = rep_len ? rep_len[i] : -1, J.hit = (int32_t)(pl.hit0 + j), J.hit0 = pl.hit0, J.n_hits = (uint32_t)n_hits;
+				++job;
+				if (!r.p) continue;
+				h.n_cigar = r.p->n_cigar, h.cig_off = cig;
+				memcpy(B.cigar + cig, r.p->cigar, (size_t)r.p->n_cigar * 4), cig += r.p->n_cigar;
+				if (!per_base) continue;
+				const uint64_t so = fi.seq_off[r.rid];
+				h.q_pos = qo;
+				memcpy(B.q + qo, t.seq + r.qs, (size_t)(r.qe - r.qs)), qo += (uint64_t)(r.qe - r.qs);
+				if (qstrand) { // format.c:343-346: mm_idx_getseq2's window, the read as it is
+					h.qsrc = (uint8_t)kTxtQAscii, h.tsrc = (uint8_t)(r.rev ? kTxtTPackedRev : kTxtTPacked);
+					h.t_pos = r.rev ? so + (fi.seq_len[r.rid] - (uint32_t)r.re) : so + (uint32_t)r.rs;
+				} else h.qsrc = (uint8_t)(r.rev ? kTxtQAsciiRev : kTxtQAscii), h.tsrc = (uint8_t)kTxtTPacked, h.t_pos = so + (uint32_t)r.rs; // format.c:347-358
+			}
+			if (n_hits == 0) {
+				RecJob &J = B.jobs[job];
+				J.name_off = pl.name_off, J.name_len = name_len, J.l_seq = t.l_seq, J.rep_len = rep_len ? rep_len[i] : -1, J.hit = -1, J.hit0 = pl.hit0, J.n_hits = 0;
+			}
+		}
+	}, 1);
+
+	const RecRes *res = be.rec_text_size(flag);
+	uint64_t dev_total = 0;
+	std::vector<uint64_t> at(sz.n_jobs + 1, 0); // where every record starts in the final text
+	for (size_t k = 0; k < sz.n_jobs; ++k) {
+		if (res[k].status != kRecOk) return host(); // a fraction outside [0, 1], or operations the walk refuses
+		B.off[k] = dev_total, dev_total += res[k].len;
+		const DevRec &d = recs[k];
+		const int i = seg_off ? seg_off[d.read] : d.read;
+		at[k + 1] = at[k] + res[k].len + (sam ? hole_len(seq[i], d.j < 0 ? nullptr : (const Reg1 *)reg[i] + d.j, flag) : 0);
+	}
+	const char *text = be.rec_text_write(dev_total);
+	const size_t total = at[sz.n_jobs];
+	if (fs.cap < total + 1) { // grow-only, as format_batch_view
+		free(fs.buf);
+		fs.cap = (total + 1) + (total + 1) / 4;
+		fs.buf = (char *)malloc(fs.cap);
+		if (!fs.buf) { fs.cap = 0; return nullptr; }
+	}
+	const long rchunk = 256, n_rchunks = ((long)sz.n_jobs + rchunk - 1) / rchunk;
+	parallel_for_side(n_threads, n_rchunks, [&](long c, int) {
+		const size_t lo = (size_t)(c * rchunk), hi = std::min(sz.n_jobs, lo + (size_t)rchunk);
+		if (!sam) { memcpy(fs.buf + at[lo], text + B.off[lo], at[hi] - at[lo]); return; } // PAF: no hole
+		for (size_t k = lo; k < hi; ++k) {
+			const DevRec &d = recs[k];
+			const int i = seg_off ? seg_off[d.read] : d.read;
+			const char *src = text + B.off[k];
+			char *w = fs.buf + at[k];
+			memcpy(w, src, res[k].before), w += res[k].before;
+			w = hole_into(w, seq[i], d.j < 0 ? nullptr : (const Reg1 *)reg[i] + d.j, flag);
+			memcpy(w, src + res[k].before, res[k].len - res[k].before);
+		}
+	}, 1);
 	fs.buf[total] = 0;
 	*out_len = total;
 	return fs.buf;

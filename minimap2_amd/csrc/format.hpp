@@ -27,6 +27,13 @@ struct FormatScratch {
 const char *format_batch_view(const FlatIndex &fi, const ref::MapOpt &opt, int n_threads, long n_frag, const int *seg_off, const int *n_seg, const ref::Bseq1 *seq, const int *n_reg,
                               void *const *reg, const int *rep_len, FormatScratch &fs, size_t *out_len);
 
+// The same text with the records written on the device (rec_text.hpp) by `be`, SEQ and QUAL filled in by the pool; *on_device = false when the
+// batch was the host writer's after all: a fragment of several segments, ds, a comment to copy, a CIGAR for the CG:B:I tag, a de / dv value
+// outside [0, 1], cs / MD of an index without sequence, a backend that does not write records.  One call at a time per backend.
+class Backend;
+const char *format_batch_dev(Backend &be, const FlatIndex &fi, const ref::MapOpt &opt, int n_threads, long n_frag, const int *seg_off, const int *n_seg, const ref::Bseq1 *seq,
+                             const int *n_reg, void *const *reg, const int *rep_len, FormatScratch &fs, size_t *out_len, bool *on_device);
+
 int format_fraction_for_test(double v, char *buf); // "%.4f" as the output stage writes it (mm2amd_format_fraction)
 
 } // namespace mm2amd

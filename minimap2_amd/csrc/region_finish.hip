@@ -23,6 +23,7 @@
 #include "region_finish.hpp"
 #include "aln_text_dev.hpp" // aln_text_kernel (the alignment's text: CIGAR string, cs, MD) is compiled with this translation unit
 #include "ksw_ll_dev.hpp"   // ksw_ll_kernel (the local score with end coordinates of ksw_ll_i16) as well
+#include "rec_text_dev.hpp"  // and rec_text_kernel (whole PAF / SAM records)
 
 namespace mm2amd {
 
