@@ -142,6 +142,18 @@ int mm2amd_ksw_ll_limits(int *strip_cols, int *wg_waves, int64_t *wg_min_cells, 
 int mm2amd_sort_pairs_u64(uint64_t *keys, uint64_t *vals, uint64_t n, int bits);
 int mm2amd_exclusive_sum_u32(const uint32_t *in, uint32_t *out, uint64_t n);
 
+/* encode_kernel (ASCII -> nt4, forward and reverse complement: align.c:1056-1061) on a batch of its own, exposed for testing: the n
+ * fragments are packed into one pinned buffer the way a mapping batch is, and the kernel runs with the launch shape the mapper uses.
+ * seqs[i] holds lens[i] bases, followed by lens2[i] bases of a mate when lens2 is not NULL and lens2[i] > 0 (the two are then units of their
+ * own, as in a batch of read pairs); lengths may be 0.  With T the sum of all lengths, out receives 2 * T + 32 bytes: 16 bytes 0xff, the query
+ * pool -- for the unit at base offset o with len bases, forward codes at 2 * o + j and the reverse complement at 2 * o + 2 * len - 1 - j --,
+ * 16 bytes 0xff: the pool is set to 0xff before the launch, so a byte the kernel did not write shows.  MM2AMD_ENCODE_BLOCKS=<n> (read once
+ * per process) replaces the grid size, for A/B runs.  mm2amd_encode_range launches the kernel on fragments [lo, hi) of that batch only, the
+ * way a mapper lane launches it on its sub-batch (offsets into the whole batch's buffers, a first word that starts anywhere): the blocks of
+ * the other fragments stay 0xff. */
+int mm2amd_encode_batch(int n, const char *const *seqs, const int32_t *lens, const int32_t *lens2, uint8_t *out);
+int mm2amd_encode_range(int n, const char *const *seqs, const int32_t *lens, const int32_t *lens2, int lo, int hi, uint8_t *out);
+
 /* Batched ksw_extz2_sse (ksw2_extz2_sse.c:25, ksw2.h:70-71): single-affine gap cost; same contract as above. */
 int mm2amd_ksw_extz2_batch(int n_jobs, const mm2amd_ksw_job_t *jobs, int8_t m, const int8_t *mat, int8_t gapo, int8_t gape,
                            mm2amd_ksw_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap);

@@ -159,6 +159,8 @@ def _bind(L):
             L.mm2amd_ksw_ll_limits.argtypes = [ip, ip, C.POINTER(C.c_int64), ip]
         L.mm2amd_sort_pairs_u64.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mm2amd_exclusive_sum_u32.argtypes = [vp, vp, C.c_uint64]
+        L.mm2amd_encode_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+        L.mm2amd_encode_range.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, vp]
         L.mm2amd_idx_str.restype = vp
         L.mm2amd_idx_str.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         L.mm2amd_idx_destroy.argtypes = [vp]
@@ -407,6 +409,31 @@ def exclusive_sum_u32(a):
     out = np.empty(x.size + 1, dtype=np.uint32)
     _check(lib().mm2amd_exclusive_sum_u32(x.ctypes.data, out.ctypes.data, x.size))
     return out
+
+
+def encode_batch(reads, lo=0, hi=None):
+    """mm2amd_encode_batch: encode_kernel, with the mapper's launch shape, on a batch of its own.  reads: bytes, or (bytes, bytes) for a pair
+    (two units).  lo / hi: launch on reads[lo:hi] only, as a mapper lane does on its sub-batch (mm2amd_encode_range).  Returns (pool, unit_off): pool a numpy uint8 array of 16 guard bytes 0xff | the query pool | 16 guard bytes 0xff (the pool
+    is 0xff wherever the kernel did not write), unit_off the units' base offsets (n_units + 1): the unit at o = unit_off[u] has its forward
+    codes at pool[16 + 2 * o + j] and its reverse complement at pool[16 + 2 * o + 2 * len - 1 - j]."""
+    import numpy as np
+    n = len(reads)
+    pairs = [r if isinstance(r, tuple) else (r, b"") for r in reads]
+    bufs = [bytes(a) + bytes(b) for a, b in pairs]
+    unit_off = [0]
+    for a, b in pairs:
+        unit_off.append(unit_off[-1] + len(a))
+        if len(b) > 0:
+            unit_off.append(unit_off[-1] + len(b))
+    seqs = (C.c_char_p * max(n, 1))(*bufs)
+    lens = (C.c_int32 * max(n, 1))(*[len(a) for a, _ in pairs])
+    lens2 = (C.c_int32 * max(n, 1))(*[len(b) for _, b in pairs])
+    out = np.empty(2 * unit_off[-1] + 32, dtype=np.uint8)
+    if lo == 0 and hi is None:
+        _check(lib().mm2amd_encode_batch(n, seqs, lens, lens2, out.ctypes.data))
+    else:
+        _check(lib().mm2amd_encode_range(n, seqs, lens, lens2, lo, n if hi is None else hi, out.ctypes.data))
+    return out, np.array(unit_off, dtype=np.int64)
 
 
 def ksw_extz2_batch(jobs, mat, gapo, gape):

@@ -371,13 +371,16 @@ public:
 			if (n_a) HIP_CHECK(hipMemcpy(all.data(), ln.d_anchors.p, n_a * sizeof(Anchor), hipMemcpyDeviceToHost));
 			static std::mutex dump_mu;
 			std::lock_guard<std::mutex> lk(dump_mu);
+			const bool dump_flags = getenv("MM2AMD_SEED_DUMP_FLAGS") != nullptr; // one more column: the anchor's tandem flag
 			if (FILE *fp = fopen(dump, "a")) {
 				for (size_t i = 0; i < n; ++i) {
 					fprintf(fp, "QR\t%s\t%d\nRS\t%d\n", read_names_.empty() || !read_names_[lo + i] ? "*" : read_names_[lo + i], P.mid_occ, h_rep[i]);
 					for (uint64_t j = a_off[i]; j < a_off[i + 1]; ++j) {
 						const Anchor &a = all[j];
-						fprintf(fp, "SD\t%s\t%d\t%c\t%d\t%d\t%d\n", (*fi_names_)[a.x << 1 >> 33].c_str(), (int32_t)a.x, "+-"[a.x >> 63], (int32_t)a.y, (int32_t)(a.y >> 32 & 0xff),
+						fprintf(fp, "SD\t%s\t%d\t%c\t%d\t%d\t%d", (*fi_names_)[a.x << 1 >> 33].c_str(), (int32_t)a.x, "+-"[a.x >> 63], (int32_t)a.y, (int32_t)(a.y >> 32 & 0xff),
 						        j == a_off[i] ? 0 : ((int32_t)a.y - (int32_t)all[j - 1].y) - ((int32_t)a.x - (int32_t)all[j - 1].x));
+						if (dump_flags) fprintf(fp, "\t%d", (int)(a.y >> 42 & 1)); // MM_SEED_TANDEM, which the reference's line leaves out
+						fputc('\n', fp);
 					}
 				}
 				fclose(fp);

@@ -12,6 +12,7 @@
 #include "aln_text.hpp"
 #include "ksw_ll.hpp"
 #include "device_sort.hpp"
+#include "seed_chain_dev.hpp"
 #include <map>
 
 namespace mm2amd { int capi_fail(int code, const std::string &msg); }
@@ -448,6 +449,48 @@ int mm2amd_exclusive_sum_u32(const uint32_t *in, uint32_t *out, uint64_t n)
 		if (n) HIP_CHECK(hipMemcpyAsync(d.p, in, n * 4, hipMemcpyHostToDevice, dc.stream));
 		device_exclusive_sum_u32(d.p, d.p, n, dc.stream);
 		HIP_CHECK(hipMemcpyAsync(out, d.p, (n + 1) * 4, hipMemcpyDeviceToHost, dc.stream));
+		HIP_CHECK(hipStreamSynchronize(dc.stream));
+		return 0;
+	});
+}
+
+int mm2amd_encode_batch(int n, const char *const *seqs, const int32_t *lens, const int32_t *lens2, uint8_t *out) { return mm2amd_encode_range(n, seqs, lens, lens2, 0, n, out); }
+
+int mm2amd_encode_range(int n, const char *const *seqs, const int32_t *lens, const int32_t *lens2, int lo, int hi, uint8_t *out)
+{
+	if (n < 0 || !out || (n > 0 && (!seqs || !lens)) || lo < 0 || hi < lo || hi > n) return fail(MM2AMD_EINVAL, "[mm2amd] encode_batch: bad arguments");
+	std::vector<uint64_t> unit_off(1, 0); // as begin_batch lays a batch out: units back to back, a pair's mate right after its first read
+	std::vector<size_t> frag_unit(1, 0);  // fragment i's first unit
+	for (int i = 0; i < n; ++i) {
+		const int32_t l2 = lens2 ? lens2[i] : 0;
+		if (lens[i] < 0 || l2 < 0 || (lens[i] + (int64_t)l2 > 0 && !seqs[i])) return fail(MM2AMD_EINVAL, "[mm2amd] encode_batch: bad read (negative length or null sequence)");
+		unit_off.push_back(unit_off.back() + (uint64_t)lens[i]);
+		if (l2 > 0) unit_off.push_back(unit_off.back() + (uint64_t)l2);
+		frag_unit.push_back(unit_off.size() - 1);
+	}
+	const uint64_t total = unit_off.back();
+	const size_t n_units = unit_off.size() - 1;
+	return guarded([&]() -> int {
+		DeviceCtx &dc = device_ctx();
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		PinBuf<char> h_ascii;
+		DevBuf<uint8_t> d_pool;
+		DevBuf<uint64_t> d_off;
+		char *h = h_ascii.ensure(total + 32, 1.0); // (the kernel reads whole aligned 16-byte words)
+		uint64_t o = 0;
+		for (int i = 0; i < n; ++i) {
+			const uint64_t l = (uint64_t)lens[i] + (uint64_t)(lens2 ? lens2[i] : 0);
+			if (l) memcpy(h + o, seqs[i], l);
+			o += l;
+		}
+		d_pool.ensure(2 * total + 32, 1.0), d_off.ensure(n_units + 1, 1.0);
+		HIP_CHECK(hipMemsetAsync(d_pool.p, 0xff, 2 * total + 32, dc.stream));
+		HIP_CHECK(hipMemcpyAsync(d_off.p, unit_off.data(), (n_units + 1) * 8, hipMemcpyHostToDevice, dc.stream));
+		SeedChainBuffers B;
+		B.n_reads = (int)(frag_unit[hi] - frag_unit[lo]), B.seq_off = d_off.p + frag_unit[lo], B.ascii = h, B.qpool = d_pool.p + 16; // (a sub-batch, as the mapper's lanes launch it: the offsets stay the batch's)
+		launch_encode(B, dc.stream);
+		HIP_CHECK(hipMemcpyAsync(out, d_pool.p, 2 * total + 32, hipMemcpyDeviceToHost, dc.stream));
 		HIP_CHECK(hipStreamSynchronize(dc.stream));
 		return 0;
 	});

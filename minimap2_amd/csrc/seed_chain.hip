@@ -37,36 +37,83 @@ static void upload_tables(hipStream_t s)
 // ---------------------------------------------------------------------------------------------------------
 // ASCII -> nt4 forward and reverse complement (align.c:1056-1061)
 // ---------------------------------------------------------------------------------------------------------
+// The launch is a small persistent grid over the sub-batch's contiguous ASCII range [seq_off[0], seq_off[n_reads]), split evenly by aligned
+// 16-byte words, not by read: the kernel waits on PCIe, and what keeps that link full is bandwidth x latency (some 0.2 MB), so kEncodeBlocks x
+// 256 lanes x kEncodeDepth loads of 16 bytes in flight do it, and the chip's other wave slots stay free for the other lanes' kernels.  (A block
+// per read put ~38 000 wavefronts of 8 VGPRs on the chip per sub-batch -- every free wave slot, for as long as the link took.)
+constexpr int kEncodeBlocks = 64, kEncodeDepth = 4;
+
+// the unit that holds byte p of the pool: the last r >= lo with seq_off[r] <= p (seq_off[lo] <= p < seq_off[n]; empty units are passed over).
+// A lane's words only move forward, so it gallops from where its previous word was found.
+__device__ __forceinline__ int encode_owner(const uint64_t *seq_off, int lo, int n, uint64_t p)
+{
+	int step = 1;
+	while (lo + step < n && seq_off[lo + step] <= p) lo += step, step <<= 1;
+	int hi = lo + step < n ? lo + step : n;
+	while (hi - lo > 1) {
+		const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+		if (seq_off[mid] <= p) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
 __global__ void __launch_bounds__(256) encode_kernel(SeedChainBuffers B)
 {
 	// B.ascii is the batch's pinned HOST buffer (read over PCIe, once): 16 bytes per lane and load, 1 KiB per wavefront request
-	const int r = blockIdx.x;
-	const uint64_t o = B.seq_off[r];
-	const int64_t len = (int64_t)(B.seq_off[r + 1] - o);
-	const char *src = B.ascii + o;
-	uint8_t *f = B.qpool + 2 * o;
-	const int64_t mis = (int64_t)((uintptr_t)src & 15u); // the read starts this far into its first aligned 16-byte word
-	const uint4 *w = (const uint4 *)(src - mis);         // (the buffer is page-aligned and padded: whole words are readable)
-	const int64_t n_words = (mis + len + 15) >> 4;
-	for (int64_t c = threadIdx.x; c < n_words; c += blockDim.x) {
-		const uint4 v = w[c];
-		const uint32_t q[4] = { v.x, v.y, v.z, v.w };
+	__shared__ uint8_t s_nt4[256];
+	s_nt4[threadIdx.x] = c_nt4[threadIdx.x];
+	__syncthreads();
+	const int n = B.n_reads;
+	const uint64_t *seq_off = B.seq_off;
+	// positions below are in the pool's coordinates shifted by sh, so that a multiple of 16 is an aligned word of the host buffer
+	const uint64_t sh = (uint64_t)((uintptr_t)B.ascii & 15u);
+	const uint4 *W = (const uint4 *)(B.ascii - sh); // (the buffer is page-aligned and padded: whole words are readable)
+	const uint64_t S = seq_off[0] + sh, E = seq_off[n] + sh;
+	if (E == S) return;
+	const uint64_t w0 = S >> 4, w1 = (E + 15) >> 4, a0 = w0 & ~63ull; // blocks start on 1 KiB, a wavefront's request size
+	const uint64_t per = ((w1 - a0 + gridDim.x - 1) / gridDim.x + 255) & ~255ull;
+	const uint64_t b0 = a0 + blockIdx.x * per, b1 = b0 + per < w1 ? b0 + per : w1;
+	uint8_t *const qp = B.qpool - 2 * sh;
+	int r = 0;
+	for (uint64_t c = b0 + threadIdx.x; c < b1; c += 256 * kEncodeDepth) {
+		uint4 v[kEncodeDepth];
 #pragma unroll
-		for (int b = 0; b < 16; ++b) {
-			const int64_t j = (c << 4) + b - mis;
-			if (j >= 0 && j < len) {
-				const uint8_t code = c_nt4[q[b >> 2] >> ((b & 3) * 8) & 0xffu];
-				f[j] = code;
-				f[2 * len - 1 - j] = code < 4 ? 3 - code : 4;
+		for (int k = 0; k < kEncodeDepth; ++k) { // all of the lane's loads go out before the first is looked at
+			const uint64_t cw = c + 256 * k;
+			v[k] = cw >= w0 && cw < b1 ? W[cw] : make_uint4(0, 0, 0, 0);
+		}
+#pragma unroll
+		for (int k = 0; k < kEncodeDepth; ++k) {
+			const uint64_t cw = c + 256 * k;
+			if (cw < w0 || cw >= b1) continue;
+			const uint64_t p0 = cw << 4 > S ? cw << 4 : S, p1 = (cw << 4) + 16 < E ? (cw << 4) + 16 : E; // the first and the last word are partial
+			r = encode_owner(seq_off, r, n, p0 - sh);
+			uint64_t o = seq_off[r] + sh, e = seq_off[r + 1] + sh; // the unit's bytes are [o, e); its block in the query pool starts at 2 * (o - sh)
+			const uint32_t q[4] = { v[k].x, v[k].y, v[k].z, v[k].w };
+#pragma unroll
+			for (int b = 0; b < 16; ++b) {
+				const uint64_t p = (cw << 4) + b;
+				if (p < p0 || p >= p1) continue;
+				while (p >= e) { ++r; o = e; e = seq_off[r + 1] + sh; } // a word that straddles units contributes to each (p < E: this ends)
+				const uint8_t code = s_nt4[q[b >> 2] >> ((b & 3) * 8) & 0xffu];
+				qp[o + p] = code;                                 // forward: 2 * o' + (p' - o') for the unshifted o' = o - sh, p' = p - sh
+				qp[o + 2 * e - 1 - p] = code < 4 ? 3 - code : 4; // reverse complement: 2 * o' + 2 * (e' - o') - 1 - (p' - o')
 			}
 		}
 	}
 }
 
+static int encode_grid_blocks()
+{
+	static const int n = [] { const char *e = getenv("MM2AMD_ENCODE_BLOCKS"); const int v = e && *e ? atoi(e) : 0; return v > 0 && v <= 4096 ? v : kEncodeBlocks; }(); // A/B: the footprint
+	return n;
+}
+
 void launch_encode(const SeedChainBuffers &B, void *stream)
 {
 	upload_tables((hipStream_t)stream);
-	hipLaunchKernelGGL(encode_kernel, dim3(B.n_reads), dim3(256), 0, (hipStream_t)stream, B);
+	if (B.n_reads <= 0) return;
+	hipLaunchKernelGGL(encode_kernel, dim3(encode_grid_blocks()), dim3(256), 0, (hipStream_t)stream, B);
 	HIP_CHECK(hipGetLastError());
 }
 
@@ -322,29 +369,85 @@ void launch_dust_filter(const SeedChainBuffers &B, void *stream)
 // ---------------------------------------------------------------------------------------------------------
 // Seed collection, one wavefront per read
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t idx_lookup(const DevIndex &I, uint64_t hash, uint32_t *off) // mm_idx_get, index.c:93-110
-{
-	const uint64_t b = hash >> I.key_shift;
-	if (b >= (1ull << I.bucket_bits)) return 0;
-	uint32_t skip = 0;
-	if (I.first) { // (round 6) the bucket's own record: empty, a single other key, or the key itself -- one sector read; only a bucket with more keys goes on
-		const IdxSlot f = I.first[b];
-		if (f.key == hash) { *off = f.off; return f.cnt & ~kIdxMoreKeys; }
-		if (!(f.cnt & kIdxMoreKeys)) return 0;
-		skip = 1; // (its first key has been looked at)
-	}
-	const uint32_t s = I.bucket_start[b] + skip, e = I.bucket_start[b + 1];
-	// (round 5) one 16-byte record per key -- key, first position, count -- so the bucket's key scan and the answer come out of the same sector:
-	// two dependent sector reads per probe (bucket_start, slots) instead of three to four (bucket_start, keys, val_off[i], val_off[i + 1])
-	for (uint32_t i = s; i < e; ++i) {
-		const IdxSlot k = I.slots[i];
-		if (k.key == hash) { *off = k.off; return k.cnt; }
-	}
-	return 0;
-}
-
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int popc_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
+
+constexpr uint32_t SD_TANDEM = 1u << 8, SD_FLT = 1u << 9, SD_SEG1 = 1u << 31; // SD_SEG1: the seed comes from the second read of a pair
+constexpr int kProbeDepth = 4; // chunks of 64 minimizers whose index probes are in flight together
+
+// The index probes of a read's n minimizers (mm_idx_get, index.c:93-110, under mm_seed_collect_all, seed.c:30-52) and the reference's m[]
+// array: the seeds that hit, in order, at o_*[0, n_m0); returns n_m0 and adds this lane's seeds above mid_occ to *n_high.  Called by whole wavefronts.
+// A read's time here is a chain of dependent global round trips, so each round takes kProbeDepth chunks of 64 minimizers and issues every
+// stage's loads for all of them before the first is looked at: the minimizers with the neighbours the tandem flag needs, then the buckets' own
+// records (round 6: an empty bucket, a single other key and the key itself are answered by that one sector), then, for the lanes whose bucket
+// holds more keys (all lanes without I.first), the bucket bounds, then the 16-byte slots (round 5: key, first position and count together).
+// Only the hits are written, compacted by one ballot per chunk and a running n_m0; the outputs are never read here and overlap no input, so
+// nothing orders one round's loads behind the previous round's stores.
+__device__ __forceinline__ int seed_probe_compact(const uint64_t *__restrict__ qx, const uint64_t *__restrict__ qy, int n, int lane, const DevIndex &I, uint32_t mid_occ,
+                                                  uint32_t *__restrict__ o_n, uint32_t *__restrict__ o_off, uint32_t *__restrict__ o_info, uint32_t *__restrict__ o_qpos, int *n_high)
+{
+	const uint64_t n_buckets = 1ull << I.bucket_bits;
+	int n_m0 = 0;
+	for (int base = 0; base < n; base += 64 * kProbeDepth) {
+		uint64_t hash[kProbeDepth], y[kProbeDepth], bkt[kProbeDepth];
+		uint32_t info[kProbeDepth], cnt[kProbeDepth], off[kProbeDepth], s[kProbeDepth], e[kProbeDepth];
+		bool live[kProbeDepth];
+#pragma unroll
+		for (int k = 0; k < kProbeDepth; ++k) {
+			const int i = base + 64 * k + lane;
+			uint64_t x = 0, xp = 0, xn = 0;
+			y[k] = 0;
+			if (i < n) {
+				x = qx[i], y[k] = qy[i];
+				if (i > 0) xp = qx[i - 1];
+				if (i < n - 1) xn = qx[i + 1];
+			}
+			hash[k] = x >> 8, bkt[k] = hash[k] >> I.key_shift;
+			live[k] = i < n && bkt[k] < n_buckets;
+			info[k] = (uint32_t)(x & 0xff);
+			if (y[k] >> 32) info[k] |= SD_SEG1;
+			if ((i > 0 && i < n && hash[k] == xp >> 8) || (i < n - 1 && hash[k] == xn >> 8)) info[k] |= SD_TANDEM;
+			cnt[k] = off[k] = 0, s[k] = e[k] = 0;
+		}
+		if (I.first) {
+			IdxSlot f[kProbeDepth];
+#pragma unroll
+			for (int k = 0; k < kProbeDepth; ++k) if (live[k]) f[k] = I.first[bkt[k]];
+#pragma unroll
+			for (int k = 0; k < kProbeDepth; ++k) {
+				if (!live[k]) continue;
+				if (f[k].key == hash[k]) off[k] = f[k].off, cnt[k] = f[k].cnt & ~kIdxMoreKeys, live[k] = false;
+				else if (!(f[k].cnt & kIdxMoreKeys)) live[k] = false;
+			}
+#pragma unroll
+			for (int k = 0; k < kProbeDepth; ++k) if (live[k]) s[k] = I.bucket_start[bkt[k]] + 1, e[k] = I.bucket_start[bkt[k] + 1]; // (its first key has been looked at)
+		} else {
+#pragma unroll
+			for (int k = 0; k < kProbeDepth; ++k) if (live[k]) s[k] = I.bucket_start[bkt[k]], e[k] = I.bucket_start[bkt[k] + 1];
+		}
+		for (bool more = true; more;) { // the buckets' key scans, one slot of every chunk per pass
+			more = false;
+#pragma unroll
+			for (int k = 0; k < kProbeDepth; ++k) {
+				if (s[k] >= e[k]) continue;
+				const IdxSlot q = I.slots[s[k]];
+				if (q.key == hash[k]) off[k] = q.off, cnt[k] = q.cnt, s[k] = e[k];
+				else more |= ++s[k] < e[k];
+			}
+		}
+#pragma unroll
+		for (int k = 0; k < kProbeDepth; ++k) { // (every lane takes part in every ballot: a chunk past n has no hit)
+			const unsigned long long hm = __ballot(cnt[k] > 0);
+			if (cnt[k] > 0) {
+				const int d = n_m0 + popc_below(hm, lane);
+				o_n[d] = cnt[k], o_off[d] = off[k], o_info[d] = info[k], o_qpos[d] = (uint32_t)y[k];
+				*n_high += cnt[k] > mid_occ;
+			}
+			n_m0 += __popcll(hm);
+		}
+	}
+	return n_m0;
+}
 
 // Cross-lane moves as DPP / v_readlane instead of ds_bpermute (what __shfl compiles to: an LDS-crossbar round trip per call, and the
 // chaining loops make dozens of dependent ones per step).  gfx9 DPP controls: row_shr:n 0x110+n, wave_shr:1 0x138, row_bcast:15 / 31 0x142 / 0x143.
@@ -380,7 +483,6 @@ __device__ __forceinline__ uint64_t lane_get_u64(uint64_t v, int l)
 	return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)v, l) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)(v >> 32), l) << 32;
 }
 constexpr int HIST_N = 2048;
-constexpr uint32_t SD_TANDEM = 1u << 8, SD_FLT = 1u << 9, SD_SEG1 = 1u << 31; // SD_SEG1: the seed comes from the second read of a pair
 
 // max-heap sift-down on (n<<32 | index) keys, used by the rare high-occurrence thinning (seed.c:56-96)
 __device__ void heap_down(uint64_t *h, int i, int n)
@@ -495,33 +597,11 @@ __global__ void __launch_bounds__(256) seed_collect_kernel(SeedChainBuffers B, D
 			n = dst;
 		}
 	}
-	// ---- index probes (mm_seed_collect_all, seed.c:30-52); entries without a hit get n = 0 ----
-	for (int i = lane; i < n; i += 64) {
-		const uint64_t x = mx[i];
-		uint32_t off = 0;
-		const uint32_t cnt = idx_lookup(I, x >> 8, &off);
-		uint32_t info = (uint32_t)(x & 0xff);
-		if (my[i] >> 32) info |= SD_SEG1;
-		if (i > 0 && x >> 8 == mx[i - 1] >> 8) info |= SD_TANDEM;
-		if (i < n - 1 && x >> 8 == mx[i + 1] >> 8) info |= SD_TANDEM;
-		sd_n[i] = cnt, sd_off[i] = off, sd_info[i] = info, sd_qpos[i] = (uint32_t)my[i];
-	}
-	WAVE_SYNC();
-	// ---- compact to the seeds that hit (the reference's m[] array), preserving order ----
-	int n_m0 = 0;
-	for (int base = 0; base < n; base += 64) {
-		const int i = base + lane;
-		uint32_t cnt = 0, off = 0, info = 0, qp = 0;
-		if (i < n) cnt = sd_n[i], off = sd_off[i], info = sd_info[i], qp = sd_qpos[i];
-		const unsigned long long hm = __ballot(cnt > 0);
-		WAVE_SYNC();
-		if (cnt > 0) { const int d = n_m0 + popc_below(hm, lane); sd_n[d] = cnt, sd_off[d] = off, sd_info[d] = info, sd_qpos[d] = qp; }
-		n_m0 += __popcll(hm);
-		WAVE_SYNC();
-	}
-	// ---- occurrence filter (seed.c:106-112) ----
+	// ---- index probes and the seeds that hit (mm_seed_collect_all, seed.c:30-52): sd_*[0, n_m0), in order; n_high of them occur more than mid_occ times ----
 	int n_high = 0;
-	for (int i = lane; i < n_m0; i += 64) n_high += sd_n[i] > (uint32_t)P.mid_occ;
+	const int n_m0 = seed_probe_compact(mx, my, n, lane, I, (uint32_t)P.mid_occ, sd_n, sd_off, sd_info, sd_qpos, &n_high);
+	WAVE_SYNC();
+	// ---- occurrence filter (seed.c:106-112) ----
 	for (int o = 32; o > 0; o >>= 1) n_high += __shfl_xor(n_high, o, 64);
 	if (n_high > 0) {
 		if (P.occ_dist > 0 && P.max_max_occ > P.mid_occ) {
