@@ -134,6 +134,33 @@ typedef struct { int32_t score, qe, te, path; } mm2amd_ll_res_t;
 int mm2amd_ksw_ll_batch(int n_jobs, const mm2amd_ll_job_t *jobs, int8_t m, const int8_t *mat, int gapo, int gape, mm2amd_ll_res_t *res);
 int mm2amd_ksw_ll_limits(int *strip_cols, int *wg_waves, int64_t *wg_min_cells, int *max_len);
 
+/* Batched sdust() (sdust.h / sdust.c:134-175): the low-complexity regions of each sequence for score threshold T and window W = 64, the window
+ * minimap2 masks its reads with before seeding (mm_dust_minier, map.c:41) -- sdust_kernel, one wavefront per sequence.  seq is ASCII, as sdust()
+ * takes it: seq_nt4_table decides, so lower case counts and every other letter, IUPAC codes included, breaks the sequence like an N.
+ * The regions of job i are pool[res[i].off, res[i].off + res[i].n), ascending, each start << 32 | finish with the values sdust() returns; the jobs'
+ * regions follow each other in job order.  pool == NULL sizes the batch: every res[i].n (and off, path) is filled, the sum of the n is the pool
+ * the real call needs.  A pool that is too small gives MM2AMD_ENOMEM with every n filled in; nothing is written at or beyond pool + pool_cap.
+ * A job of length 0 has no regions.  res[i].path says which launch class scanned job i -- a function of the job alone:
+ *   MM2AMD_SDUST_PATH_NARROW  the list of perfect intervals never held more than narrow_cap entries (it lives in LDS, a dword an entry);
+ *   MM2AMD_SDUST_PATH_WIDE    it did: the job stopped there, listed itself on the device, and was scanned again from its first base with
+ *                             wide_cap entries, which no list exceeds (an entry lives at most 62 steps and a step adds at most 62).
+ * MM2AMD_EINVAL for T <= 0, a null argument, a negative length or a length above max_len; n_jobs == 0 returns 0; MM2AMD_ENODEV without a device.
+ * Device buffers are kept between calls.  mm2amd_sdust_limits reports narrow_cap (as in force, see below), wide_cap (4096) and max_len
+ * (2^30); any pointer may be NULL.  Two environment variables are read at every call: MM2AMD_SDUST_NARROW_CAP=<n> replaces the narrow
+ * capacity (1 .. wide_cap; tests send 100-base reads through the wide class with it); MM2AMD_SDUST_NO_NARROW=1 sends every job through the
+ * wide class at once (the A/B of tools/sdust_bench.py).
+ * mm2amd_sdust_host_batch is a benchmark and test hook, not part of the drop-in surface: the host's routine (sdust_scan, the default of the
+ * `-T` path) on n_threads threads with the same results (path is not set), which tools/sdust_bench.py times against the kernel; it needs no
+ * device.  *core_seconds, unless NULL, receives the threads' summed time inside the scans. */
+#define MM2AMD_SDUST_PATH_NARROW 0
+#define MM2AMD_SDUST_PATH_WIDE   1
+typedef struct { const char *seq; int32_t len; } mm2amd_sdust_job_t;
+typedef struct { uint64_t off; uint32_t n; int32_t path; } mm2amd_sdust_res_t;
+int mm2amd_sdust_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, mm2amd_sdust_res_t *res, uint64_t *pool, size_t pool_cap);
+int mm2amd_sdust_limits(int *narrow_cap, int *wide_cap, int *max_len);
+int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, int n_threads, mm2amd_sdust_res_t *res, uint64_t *pool, size_t pool_cap,
+                            double *core_seconds);
+
 /* The two device-wide primitives of the index build (device_sort.hip), exposed for testing.  mm2amd_sort_pairs_u64: n (key, value) pairs
  * sorted in place by key bits [0, bits), stably -- what radix_sort_128x (ksort.h:101-151, instantiated at sketch.c:13 and called per bucket
  * at index.c:236) yields for pairs whose input order is ascending in the value: rs_hist / rs_chunk_scan / rs_block_offsets / rs_scatter

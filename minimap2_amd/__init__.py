@@ -50,6 +50,14 @@ class LlRes(C.Structure):  # mm2amd_ll_res_t
     _fields_ = [("score", C.c_int32), ("qe", C.c_int32), ("te", C.c_int32), ("path", C.c_int32)]
 
 
+class SdustJob(C.Structure):  # mm2amd_sdust_job_t
+    _fields_ = [("seq", C.c_char_p), ("len", C.c_int32)]
+
+
+class SdustRes(C.Structure):  # mm2amd_sdust_res_t
+    _fields_ = [("off", C.c_uint64), ("n", C.c_uint32), ("path", C.c_int32)]
+
+
 class KswRes(C.Structure):  # mm2amd_ksw_res_t
     _fields_ = [(n, C.c_int32) for n in ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score",
                                          "n_cigar", "reach_end")] + [("cigar_off", C.c_uint32)]
@@ -115,6 +123,7 @@ TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD = 0, 1, 2, 3  # MM2AMD_TXT_*
 FMT_PATH_DEVICE, FMT_PATH_HOST = 0, 1  # MM2AMD_FMT_PATH_*: who wrote the text of mm_gpu_format_batch_dev
 LL_QREV, LL_QCOMP, LL_TREV = 1, 2, 4  # MM2AMD_LL_*
 LL_PATH_WAVE, LL_PATH_WG, LL_PATH_HOST = 0, 1, 2  # MM2AMD_LL_PATH_*
+SDUST_PATH_NARROW, SDUST_PATH_WIDE = 0, 1  # MM2AMD_SDUST_PATH_*
 
 _lib = None
 
@@ -157,6 +166,10 @@ def _bind(L):
         if hasattr(L, "mm2amd_ksw_ll_batch"):
             L.mm2amd_ksw_ll_batch.argtypes = [C.c_int, C.POINTER(LlJob), C.c_int8, C.c_char_p, C.c_int, C.c_int, C.POINTER(LlRes)]
             L.mm2amd_ksw_ll_limits.argtypes = [ip, ip, C.POINTER(C.c_int64), ip]
+        if hasattr(L, "mm2amd_sdust_batch"):
+            L.mm2amd_sdust_batch.argtypes = [C.c_int, C.POINTER(SdustJob), C.c_int, C.POINTER(SdustRes), vp, C.c_size_t]
+            L.mm2amd_sdust_limits.argtypes = [ip, ip, ip]
+            L.mm2amd_sdust_host_batch.argtypes = [C.c_int, C.POINTER(SdustJob), C.c_int, C.c_int, C.POINTER(SdustRes), vp, C.c_size_t, C.POINTER(C.c_double)]
         L.mm2amd_sort_pairs_u64.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mm2amd_exclusive_sum_u32.argtypes = [vp, vp, C.c_uint64]
         L.mm2amd_encode_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
@@ -381,6 +394,59 @@ def ksw_ll_limits():
     return {"strip_cols": a.value, "wg_waves": b.value, "wg_min_cells": c.value, "max_len": d.value}
 
 
+def _sdust_jobs(seqs):
+    n = len(seqs)
+    arr = (SdustJob * max(n, 1))()
+    keep = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    for i, b in enumerate(keep):
+        arr[i].seq, arr[i].len = b, len(b)
+    return arr, keep
+
+
+def _sdust_regions(call, n, keep):
+    """per job an (n, 2) int32 array of (start, finish), and the result records.  One call: a region is at least four bases long and two regions
+    never touch, so a sequence of len bases has at most len // 4 + 1 of them and the pool can be sized without the sizing call (a second scan)."""
+    import numpy as np
+    res = (SdustRes * max(n, 1))()
+    cap = sum(len(b) // 4 + 1 for b in keep)
+    pool = np.zeros(max(cap, 1), dtype=np.uint64)
+    _check(call(res, pool.ctypes.data, cap))
+    out = []
+    for r in res[:n]:
+        v = pool[r.off:r.off + r.n]
+        out.append(np.stack([(v >> np.uint64(32)).astype(np.int32), (v & np.uint64(0xffffffff)).astype(np.int32)], axis=1).reshape(-1, 2))
+    return out, res
+
+
+def sdust_batch(seqs, T=20, paths=False):
+    """mm2amd_sdust_batch: seqs a list of bytes / str (ASCII, as the reference's sdust() takes them).  Returns per sequence an (n, 2) int32
+    array of the (start, finish) pairs sdust(seq, T, W = 64) returns (sdust.c:134-175; sdust_kernel, one wavefront per sequence); with
+    paths=True also the list of launch classes that scanned them (SDUST_PATH_NARROW / SDUST_PATH_WIDE)."""
+    n = len(seqs)
+    arr, keep = _sdust_jobs(seqs)
+    L = lib()
+    out, res = _sdust_regions(lambda res, pool, cap: L.mm2amd_sdust_batch(n, arr, T, res, pool, cap), n, keep)
+    return (out, [r.path for r in res[:n]]) if paths else out
+
+
+def sdust_host_batch(seqs, T=20, n_threads=1):
+    """mm2amd_sdust_host_batch: the same regions from the host's sdust_scan on n_threads threads; returns (regions, core_seconds)"""
+    n = len(seqs)
+    arr, keep = _sdust_jobs(seqs)
+    L = lib()
+    cs = C.c_double(0)
+    out, _ = _sdust_regions(lambda res, pool, cap: L.mm2amd_sdust_host_batch(n, arr, T, n_threads, res, pool, cap, C.byref(cs)), n, keep)
+    return out, cs.value
+
+
+def sdust_limits():
+    """mm2amd_sdust_limits: narrow_cap (as in force), wide_cap, max_len -- a sequence takes the wide class iff its list of perfect intervals
+    ever held more than narrow_cap entries"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().mm2amd_sdust_limits(C.byref(a), C.byref(b), C.byref(c)))
+    return {"narrow_cap": a.value, "wide_cap": b.value, "max_len": c.value}
+
+
 def hits_text(idx, hits, reads, what, is_qstrand=False):
     """mm2amd_hits_text_batch: idx an index handle, hits the addresses of mm_reg1_t records, reads each hit's read (bytes).  Returns each
     hit's text, '' for a hit without base-level alignment (mm_gen_cs_ds_or_MD, format.c:364-375)."""
@@ -573,13 +639,14 @@ class Aligner(object):
     fn_idx_in: instead of seq, a file -- a minimap2 index (.mmi, read by mm2amd_idx_load; part: which part of a multi-part file, required when
     there is more than one; the file's k, w and flags replace the preset's) or FASTA / FASTQ, plain or gzip.  fn_idx_out: write the index there
     as a .mmi (mm2amd_idx_dump) once it is built.  extra_flags: MM_F_* bits ORed into map_opt.flag (mappy's parameter of the same name).
+    sdust_thres: minimap2's -T (minimizers lying mostly in SDUST-masked stretches of a read are dropped; 0 = off).
     n_gpus / device_ids: map every batch on several GPUs of this process (mm_gpu_init_index_multi: index replicated, reads sharded
     by bases; an ordinal may repeat).  Only one Aligner can be the active mapper of the process at a time (the drop-in boundary is
     a process-wide context, like the reference's pipeline): creating a second one makes the first inactive -- its map calls raise,
     and closing or collecting it leaves the new context alone."""
 
     def __init__(self, seq=None, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None,
-                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0):
+                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0):
         L = lib()
         self._generation, self._idx, self._staged = 0, None, None  # close() must work on a half-built object
         self.last_format_path = None  # FMT_PATH_* of the last format_raw(device=True)
@@ -598,6 +665,8 @@ class Aligner(object):
         if sam:
             self.map_opt.flag |= F_OUT_SAM | F_CIGAR
         self.map_opt.flag |= extra_flags  # MM_F_* bits beyond the preset's (mappy.Aligner's extra_flags)
+        if sdust_thres:
+            self.map_opt.sdust_thres = sdust_thres
         from_index = fn_idx_in is not None and idx_is_idx(fn_idx_in)
         if from_index:
             # a prebuilt index: its k, w and flag win over the preset's, as in the reference's reader (mm_idx_reader_read, index.c:621-635)

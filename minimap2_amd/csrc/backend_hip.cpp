@@ -25,12 +25,15 @@
 #include "threads.hpp"
 #include "trace.hpp"
 #include "sdust_core.hpp"
+#include "sdust.hpp"
 
 namespace mm2amd {
 
 extern const uint8_t kNt4Table[256];
 
 namespace {
+
+bool env_on(const char *name) { const char *e = getenv(name); return e && *e && strcmp(e, "0") != 0; }
 
 struct Lane {
 	int id = 0;
@@ -39,6 +42,9 @@ struct Lane {
 	SeedChainBuffers B{};
 	KswRunner ksw;
 	DevBuf<uint64_t> d_a_off, d_mp_off, d_mz_x, d_mz_y, d_minipos, d_skey_in, d_sval_in, d_skey_out, d_sval_out;
+	DevBuf<uint32_t> d_sdust_list;
+	DevBuf<SdustCounters> d_sdust_cnt;
+	PinBuf<SdustCounters> h_sdust_cnt;
 	DevBuf<uint32_t> d_mz_cnt, d_sd_n, d_sd_off, d_sd_aoff, d_sd_qpos, d_sd_info, d_n_anchor, d_n_minipos, d_n_seedhit, d_tie;
 	DevBuf<int32_t> d_rep_len, d_f, d_p, d_t;
 	DevBuf<Anchor> d_anchors;
@@ -292,7 +298,29 @@ public:
 		kp.begin(st); launch_sketch(Bu, P, max_len, st); kp.end(st, "sketch_kernel", L + 16.0 * est_mz);
 		if (has_pairs_) // seed_collect joins the minimizer lists of a pair's two units (collect_minimizers, map.c:59-72); indices are batch-wide
 			B.unit_first = d_unit_first_.p + lo, B.unit_off = d_unit_off_.p, B.unit_cnt = ln.d_mz_cnt.p - ulo, B.mz_cnt = nullptr;
-		if (P.sdust_thres > 0) { // -T: drop minimizers in low-complexity regions (the seed arrays are still unused: they carry the regions)
+		// -T: drop minimizers in low-complexity regions (the seed arrays are still unused: they carry the regions).  MM2AMD_DEVICE_SDUST=1: the regions
+		// come from sdust_kernel on the encoded reads, in its two launch classes (sdust.hpp), on this stream; otherwise from the host threads
+		const bool dev_sdust = P.sdust_thres > 0 && env_on("MM2AMD_DEVICE_SDUST"), sdust_no_narrow = env_on("MM2AMD_SDUST_NO_NARROW"); // (read at every call, as mm2amd_sdust_batch reads its two)
+		if (dev_sdust) {
+			ln.d_sdust_list.ensure(n_unit), ln.d_sdust_cnt.ensure(1);
+			HIP_CHECK(hipMemsetAsync(ln.d_sdust_cnt.p, 0, sizeof(SdustCounters), st));
+			SdustParams S;
+			S.codes = B.qpool, S.off = Bu.seq_off, S.code_mul = 2, S.n_reads = (int)n_unit, S.T = P.sdust_thres < kSdustMaxT ? P.sdust_thres : kSdustMaxT;
+			S.reg_n = B.sd_n, S.reg_s = B.sd_off, S.reg_e = B.sd_aoff, S.wide_list = ln.d_sdust_list.p, S.cnt = ln.d_sdust_cnt.p;
+			const char *e_cap = getenv("MM2AMD_SDUST_NARROW_CAP");
+			const long cap = e_cap && *e_cap ? strtol(e_cap, nullptr, 10) : kSdustNarrowCap;
+			if (sdust_no_narrow) {
+				S.cap = kSdustWideCap, S.wide = 2;
+				kp.begin(st); sdust_launch(S, 0, st); kp.end(st, "sdust_kernel[wide]", 0.0);
+			} else {
+				S.cap = (int)(cap < 1 ? 1 : cap > kSdustWideCap ? kSdustWideCap : cap), S.wide = 0;
+				kp.begin(st); sdust_launch(S, 0, st); kp.end(st, "sdust_kernel[narrow]", 0.0);
+				S.cap = kSdustWideCap, S.wide = 1; // the reads that stopped: the launch reads the list's length on the device
+				kp.begin(st); sdust_launch(S, 0, st); kp.end(st, "sdust_kernel[wide]", 0.0);
+			}
+			HIP_CHECK(hipMemcpyAsync(ln.h_sdust_cnt.ensure(1), ln.d_sdust_cnt.p, sizeof(SdustCounters), hipMemcpyDeviceToHost, st)); // (read after the wait below)
+			kp.begin(st); launch_dust_filter(B, st); kp.end(st, "dust_filter_kernel", 16.0 * est_mz);
+		} else if (P.sdust_thres > 0) {
 			uint32_t *h_n = ln.h_dust_n.ensure(cap_mz + 1), *h_s = ln.h_dust_s.ensure(cap_mz + 1), *h_e = ln.h_dust_e.ensure(cap_mz + 1);
 			const char *asc = h_ascii_.p;
 			parallel_for(n_threads, (long)n_unit, [&](long u, int) { // sdust_core per read on the host, while the sketch kernel runs
@@ -323,6 +351,12 @@ public:
 		HIP_CHECK(hipMemcpyAsync(h_nmp, ln.d_n_minipos.p, n * 4, hipMemcpyDeviceToHost, st));
 		HIP_CHECK(hipMemcpyAsync(h_rep, ln.d_rep_len.p, n * 4, hipMemcpyDeviceToHost, st));
 		stream_wait(st);
+		if (dev_sdust) { // bases each class scanned: a read that stopped counts up to there for the narrow class and whole for the wide one
+			const SdustCounters &c = *ln.h_sdust_cnt.p;
+			if (c.err) throw HipError("[mm2amd] sdust_kernel: a list of perfect intervals outgrew the wide capacity");
+			kp.add_units("sdust_kernel[wide]", (double)c.wide_bases);
+			if (!sdust_no_narrow) kp.add_units("sdust_kernel[narrow]", L - (double)c.wide_bases + (double)c.narrow_partial);
+		}
 		Trace::get().add(lane_id, "gpu:sketch+collect", tt, Trace::now()); tt = Trace::now();
 		std::vector<uint64_t> &a_off = ln.a_off, &mp_off = ln.mp_off;
 		a_off.resize(n + 1), mp_off.resize(n + 1);

@@ -11,12 +11,17 @@
 #include "region_finish.hpp"
 #include "aln_text.hpp"
 #include "ksw_ll.hpp"
+#include "sdust.hpp"
+#include "sdust_core.hpp"
+#include "threads.hpp"
+#include "trace.hpp"
 #include "device_sort.hpp"
 #include "seed_chain_dev.hpp"
 #include <map>
 
 namespace mm2amd { int capi_fail(int code, const std::string &msg); }
 using namespace mm2amd;
+namespace mm2amd { extern const uint8_t kNt4Table[256]; }
 
 namespace {
 
@@ -42,6 +47,33 @@ constexpr size_t kLlBndBudget = (size_t)1 << 26; // words of boundary columns pe
 
 bool ll_no_wg() { const char *e = getenv("MM2AMD_LL_NO_WG"); return e && *e && strcmp(e, "0") != 0; }
 int64_t ll_wg_min_cells() { const char *e = getenv("MM2AMD_LL_WG_MIN_CELLS"); return e && *e ? (int64_t)strtoll(e, nullptr, 10) : kLlWgMinCells; }
+
+struct SdustApiState { // mm2amd_sdust_batch: kept between calls
+	DevBuf<uint8_t> d_codes;
+	DevBuf<uint64_t> d_off, d_out_off, d_out;
+	DevBuf<uint32_t> d_reg_n, d_reg_s, d_reg_e, d_list, d_cnt_out;
+	DevBuf<SdustCounters> d_cnt;
+	PinBuf<uint8_t> h_codes;
+	PinBuf<uint64_t> h_off;
+	PinBuf<uint32_t> h_list;
+};
+SdustApiState &sdust_state() { static SdustApiState s; return s; }
+
+bool sdust_no_narrow() { const char *e = getenv("MM2AMD_SDUST_NO_NARROW"); return e && *e && strcmp(e, "0") != 0; }
+int sdust_narrow_cap()
+{
+	const char *e = getenv("MM2AMD_SDUST_NARROW_CAP");
+	const long v = e && *e ? strtol(e, nullptr, 10) : kSdustNarrowCap;
+	return (int)(v < 1 ? 1 : v > kSdustWideCap ? kSdustWideCap : v);
+}
+
+int sdust_check_args(const char *who, int n_jobs, const mm2amd_sdust_job_t *jobs, int T, const mm2amd_sdust_res_t *res)
+{
+	if (n_jobs < 0 || T <= 0 || (n_jobs > 0 && (!jobs || !res))) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (T must be positive)");
+	for (int i = 0; i < n_jobs; ++i)
+		if (jobs[i].len < 0 || jobs[i].len > kSdustMaxLen || (jobs[i].len > 0 && !jobs[i].seq)) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad job (negative or excessive length, or null sequence)");
+	return 0;
+}
 
 template <typename F>
 int guarded(F &&f)
@@ -413,6 +445,128 @@ int mm2amd_ksw_ll_batch(int n_jobs, const mm2amd_ll_job_t *jobs, int8_t m, const
 			kernel_profiler(0).collect();
 			for (const LlJob &o : dj) res[o.out].score = hr[o.out].score, res[o.out].qe = hr[o.out].qe, res[o.out].te = hr[o.out].te;
 		}
+		return 0;
+	});
+}
+
+int mm2amd_sdust_limits(int *narrow_cap, int *wide_cap, int *max_len)
+{
+	if (narrow_cap) *narrow_cap = sdust_narrow_cap();
+	if (wide_cap) *wide_cap = kSdustWideCap;
+	if (max_len) *max_len = kSdustMaxLen;
+	return 0;
+}
+
+int mm2amd_sdust_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, mm2amd_sdust_res_t *res, uint64_t *pool, size_t pool_cap)
+{
+	if (const int rc = sdust_check_args("sdust_batch", n_jobs, jobs, T, res)) return rc;
+	if (n_jobs == 0) return 0;
+	return guarded([&]() -> int {
+		DeviceCtx &dc = device_ctx();
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		SdustApiState &d = sdust_state();
+		const size_t n = (size_t)n_jobs;
+		uint64_t *const h_off = d.h_off.ensure(2 * (n + 1)); // the jobs' base offsets, then their offsets in the pool
+		h_off[0] = 0;
+		for (size_t i = 0; i < n; ++i) h_off[i + 1] = h_off[i] + (uint64_t)jobs[i].len;
+		const uint64_t total = h_off[n];
+		uint8_t *const h_codes = d.h_codes.ensure(total + 1);
+		for (size_t i = 0; i < n; ++i) for (int32_t k = 0; k < jobs[i].len; ++k) h_codes[h_off[i] + k] = kNt4Table[(uint8_t)jobs[i].seq[k]];
+		d.d_codes.ensure(total + 1), d.d_off.ensure(n + 1), d.d_out_off.ensure(n + 1), d.d_reg_n.ensure(total + 1), d.d_reg_s.ensure(total + 1), d.d_reg_e.ensure(total + 1);
+		d.d_list.ensure(n), d.d_cnt_out.ensure(n), d.d_cnt.ensure(1);
+		HIP_CHECK(hipMemcpyAsync(d.d_codes.p, h_codes, total + 1, hipMemcpyHostToDevice, dc.stream));
+		HIP_CHECK(hipMemcpyAsync(d.d_off.p, h_off, (n + 1) * 8, hipMemcpyHostToDevice, dc.stream));
+		HIP_CHECK(hipMemsetAsync(d.d_cnt.p, 0, sizeof(SdustCounters), dc.stream));
+		SdustParams P;
+		P.codes = d.d_codes.p, P.off = d.d_off.p, P.code_mul = 1, P.n_reads = n_jobs, P.T = T < kSdustMaxT ? T : kSdustMaxT;
+		P.reg_n = d.d_reg_n.p, P.reg_s = d.d_reg_s.p, P.reg_e = d.d_reg_e.p, P.wide_list = d.d_list.p, P.cnt = d.d_cnt.p;
+		KernelProfiler &prof = kernel_profiler(0);
+		SdustCounters hc;
+		memset(&hc, 0, sizeof hc);
+		uint32_t *const h_list = d.h_list.ensure(2 * n); // the listed jobs, then every job's number of regions
+		for (size_t i = 0; i < n; ++i) res[i].path = MM2AMD_SDUST_PATH_NARROW;
+		if (sdust_no_narrow()) {
+			P.cap = kSdustWideCap, P.wide = 2;
+			prof.begin(dc.stream);
+			sdust_launch(P, 0, dc.stream);
+			prof.end(dc.stream, "sdust_kernel[wide]", 0.0, (double)total);
+			for (size_t i = 0; i < n; ++i) res[i].path = MM2AMD_SDUST_PATH_WIDE;
+		} else {
+			P.cap = sdust_narrow_cap(), P.wide = 0;
+			prof.begin(dc.stream);
+			sdust_launch(P, 0, dc.stream);
+			prof.end(dc.stream, "sdust_kernel[narrow]", 0.0, 0.0);
+			HIP_CHECK(hipMemcpyAsync(&hc, d.d_cnt.p, sizeof hc, hipMemcpyDeviceToHost, dc.stream));
+			HIP_CHECK(hipStreamSynchronize(dc.stream));
+			if (hc.n_wide > (uint32_t)n_jobs) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: the device's list of wide jobs is longer than the batch");
+			double wide_bases = 0;
+			if (hc.n_wide) { // the jobs that stopped, scanned again with the full list: a launch of exactly that many wavefronts
+				HIP_CHECK(hipMemcpyAsync(h_list, d.d_list.p, (size_t)hc.n_wide * 4, hipMemcpyDeviceToHost, dc.stream));
+				P.cap = kSdustWideCap, P.wide = 1;
+				prof.begin(dc.stream);
+				sdust_launch(P, (int)std::min<uint32_t>(hc.n_wide, (uint32_t)kSdustWideGrid), dc.stream);
+				prof.end(dc.stream, "sdust_kernel[wide]", 0.0, 0.0);
+				HIP_CHECK(hipStreamSynchronize(dc.stream));
+				for (uint32_t k = 0; k < hc.n_wide; ++k) {
+					if (h_list[k] >= (uint32_t)n_jobs) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: the device listed a job outside the batch");
+					res[h_list[k]].path = MM2AMD_SDUST_PATH_WIDE, wide_bases += (double)jobs[h_list[k]].len;
+				}
+				prof.add_units("sdust_kernel[wide]", wide_bases);
+			}
+			prof.add_units("sdust_kernel[narrow]", (double)total - wide_bases + (double)hc.narrow_partial);
+		}
+		// every job's number of regions, the offsets they give, then the regions themselves
+		sdust_count_launch(P, d.d_cnt_out.p, dc.stream);
+		uint32_t *const h_n = h_list + n;
+		HIP_CHECK(hipMemcpyAsync(h_n, d.d_cnt_out.p, n * 4, hipMemcpyDeviceToHost, dc.stream));
+		HIP_CHECK(hipMemcpyAsync(&hc, d.d_cnt.p, sizeof hc, hipMemcpyDeviceToHost, dc.stream));
+		HIP_CHECK(hipStreamSynchronize(dc.stream));
+		prof.collect();
+		if (hc.err) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: a list of perfect intervals outgrew the wide capacity");
+		uint64_t *const out_off = h_off + n + 1;
+		uint64_t n_out = 0;
+		for (size_t i = 0; i < n; ++i) {
+			if (h_n[i] > (uint32_t)jobs[i].len) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: more regions than bases");
+			out_off[i] = n_out, res[i].off = n_out, res[i].n = h_n[i];
+			n_out += h_n[i];
+		}
+		if (!pool || n_out == 0) return 0;
+		if (n_out > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] sdust_batch: pool too small (a call with pool == NULL gives the counts)");
+		d.d_out.ensure(n_out);
+		HIP_CHECK(hipMemcpyAsync(d.d_out_off.p, out_off, n * 8, hipMemcpyHostToDevice, dc.stream));
+		sdust_pack_launch(P, d.d_out_off.p, d.d_out.p, dc.stream);
+		HIP_CHECK(hipMemcpyAsync(pool, d.d_out.p, n_out * 8, hipMemcpyDeviceToHost, dc.stream));
+		HIP_CHECK(hipStreamSynchronize(dc.stream));
+		return 0;
+	});
+}
+
+int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, int n_threads, mm2amd_sdust_res_t *res, uint64_t *pool, size_t pool_cap,
+                            double *core_seconds)
+{
+	if (const int rc = sdust_check_args("sdust_host_batch", n_jobs, jobs, T, res)) return rc;
+	if (core_seconds) *core_seconds = 0;
+	if (n_jobs == 0) return 0;
+	return guarded([&]() -> int {
+		std::vector<std::vector<uint64_t>> regs((size_t)n_jobs);
+		std::vector<double> busy((size_t)std::max(n_threads, 1), 0.0);
+		parallel_for(n_threads, (long)n_jobs, [&](long i, int tid) {
+			const double t0 = Trace::now();
+			thread_local std::vector<SdustState::Perf> perf(SdustState::PCAP);
+			std::vector<uint8_t> codes((size_t)jobs[i].len + 1);
+			for (int32_t k = 0; k < jobs[i].len; ++k) codes[k] = kNt4Table[(uint8_t)jobs[i].seq[k]];
+			SdustState S;
+			S.P = perf.data();
+			sdust_scan(codes.data(), jobs[i].len, T, S, [&](int s0, int e0) { regs[i].push_back((uint64_t)(uint32_t)s0 << 32 | (uint32_t)e0); });
+			busy[tid] += Trace::now() - t0;
+		}, 1);
+		uint64_t n_out = 0;
+		for (int i = 0; i < n_jobs; ++i) res[i].off = n_out, res[i].n = (uint32_t)regs[i].size(), res[i].path = -1, n_out += regs[i].size();
+		if (core_seconds) for (double b : busy) *core_seconds += b;
+		if (!pool || n_out == 0) return 0;
+		if (n_out > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] sdust_host_batch: pool too small (a call with pool == NULL gives the counts)");
+		for (int i = 0; i < n_jobs; ++i) if (!regs[i].empty()) memcpy(pool + res[i].off, regs[i].data(), regs[i].size() * 8);
 		return 0;
 	});
 }

@@ -17,6 +17,7 @@
 #include "heap_order.hpp"
 #include "sdust_core.hpp"
 #include "sketch_dev.hpp"
+#include "sdust_dev.hpp"     // sdust_kernel (the masked regions themselves, one wavefront per read) as well
 #include "kernel_prof.hpp"
 
 namespace mm2amd {
@@ -338,10 +339,10 @@ void launch_sketch(const SeedChainBuffers &B, const SeedChainParams &P, int max_
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// SDUST (-T): the masked regions of every read are found on host threads (sdust_core.hpp: a sequential automaton with a sorted
-// interval list that is rewritten at every base -- the wrong shape for a lane) while the sketch kernel runs, and uploaded into the
-// read's still-unused seed slots: sd_n[o] = number of regions, sd_off[o + u] / sd_aoff[o + u] = start / end of region u.  This kernel
-// only drops the minimizers that lie mostly inside masked regions (mm_dust_minier, map.c:34-57), one thread per read.
+// SDUST (-T): the masked regions of every read are in the read's still-unused seed slots -- sd_n[o] = number of regions, sd_off[o + u] /
+// sd_aoff[o + u] = start / end of region u -- written either by sdust_kernel (sdust_dev.hpp, MM2AMD_DEVICE_SDUST=1: one wavefront per read, the
+// 64-base window across the lanes) or by the host threads' sdust_scan (sdust_core.hpp, one thread per read, the default) and uploaded.  This
+// kernel only drops the minimizers that lie mostly inside masked regions (mm_dust_minier, map.c:34-57), one thread per read.
 // ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) dust_filter_kernel(SeedChainBuffers B)
 {
