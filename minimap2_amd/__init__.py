@@ -941,13 +941,14 @@ class Aligner(object):
             self.free_raw(n_reg, reg)
 
     def last_stats(self):
-        v = (C.c_double * 40)()
-        k = lib().mm2amd_last_stats(v, 40)
+        v = (C.c_double * 48)()
+        k = lib().mm2amd_last_stats(v, 48)
         names = ["t_seed_chain", "t_host_pre", "t_plan", "t_ksw", "t_consume", "t_finish", "n_jobs", "n_rounds", "dp_cells", "dev_allocs", "pin_allocs",
                  "alloc_ns", "cpu_seed_chain", "cpu_host_pre", "cpu_plan", "cpu_ksw", "cpu_consume", "cpu_finish", "n_long_join_dev", "n_long_join_host",
                  "drv_cpu_seed_chain", "drv_cpu_host_pre", "drv_cpu_plan", "drv_cpu_ksw", "drv_cpu_consume", "drv_cpu_finish", "n_early_sub",
                  "n_region_reads_dev", "n_region_reads_host", "n_band128", "n_band256", "n_band_widened", "n_band_rectangle",
-                 "arena_dev_bytes", "arena_pin_bytes", "arena_dev_used", "arena_pin_used", "n_band512", "n_band_rectangle_big"]
+                 "arena_dev_bytes", "arena_pin_bytes", "arena_dev_used", "arena_pin_used", "n_band512", "n_band_rectangle_big",
+                 "n_anchors_prune_in", "n_anchors_prune_kept", "n_reads_prune_redo"]  # (the last three: process-wide since start, like the band counters)
         return dict(zip(names, list(v)[:k]))
 
 

@@ -45,12 +45,13 @@ struct Lane {
 	DevBuf<uint32_t> d_sdust_list;
 	DevBuf<SdustCounters> d_sdust_cnt;
 	PinBuf<SdustCounters> h_sdust_cnt;
-	DevBuf<uint32_t> d_mz_cnt, d_sd_n, d_sd_off, d_sd_aoff, d_sd_qpos, d_sd_info, d_n_anchor, d_n_minipos, d_n_seedhit, d_tie;
+	DevBuf<uint32_t> d_mz_cnt, d_sd_n, d_sd_off, d_sd_aoff, d_sd_qpos, d_sd_info, d_n_anchor, d_n_minipos, d_n_seedhit, d_tie, d_nkept;
 	DevBuf<int32_t> d_rep_len, d_f, d_p, d_t;
 	DevBuf<Anchor> d_anchors;
 	DevBuf<uint8_t> d_tbytes;
 	DevBuf<uint32_t> d_sort_list;
 	PinBuf<uint32_t> h_sort_list;
+	DevBuf<Anchor> d_dump_anchors;             // MM2AMD_CHAIN_DUMP with pruning: the unpruned sort's output, for the IN blocks
 	DevBuf<uint32_t> d_pieces;                 // the chaining kernels' work list when a read of the launch is cut into pieces (make_pieces)
 	PinBuf<uint32_t> h_pieces, h_lj_pieces;
 	DevBuf<Anchor> d_lj_out_a;                 // long-join re-chaining (second backtrack's anchors; the first one's are its input)
@@ -83,7 +84,7 @@ struct Lane {
 	DevBuf<Anchor> d_bt_out_a;
 	DevBuf<uint64_t> d_bt_out_u, d_bt_aoff, d_bt_uoff;
 	DevBuf<int32_t> d_bt_nu, d_bt_nv;
-	PinBuf<uint32_t> h_na, h_nmp, h_dust_n, h_dust_s, h_dust_e, h_tie;
+	PinBuf<uint32_t> h_na, h_nmp, h_dust_n, h_dust_s, h_dust_e, h_tie, h_nkept;
 	std::vector<uint64_t> a_off, mp_off;
 	~Lane() { if (stream) (void)hipStreamDestroy(stream); }
 };
@@ -373,6 +374,22 @@ public:
 		B.sort_key_in = ln.d_skey_in.p, B.sort_val_in = ln.d_sval_in.p, B.sort_key_out = ln.d_skey_out.p, B.sort_val_out = ln.d_sval_out.p, B.tie_flag = ln.d_tie.p;
 		B.tie_list = ln.d_tie.p + n, B.tie_count = ln.d_tie.p + 2 * n;
 		B.rid_bits = rid_bits_;
+		// Anchors with no other anchor of their strand and target inside the chaining window go before the sort (seed_chain.hip: anchor_sort_prune_kernel) where
+		// that is exact: mg_lchain_dp's fill (not the RMQ chainer, not a caller that wants every sorted anchor), one segment per read, every span = k (no HPC)
+		// below min_chain_score (an isolated anchor is no chain end), the radix sort's order (not the heap merge's), and no seed dump, which is the reference's
+		// full list.  MM2AMD_ANCHOR_PRUNE=0: the A/B switch.  MM2AMD_PRUNE_BINS / MM2AMD_PRUNE_CAP (tests): a smaller presence table / survivor capacity.
+		static const bool prune_env = !(getenv("MM2AMD_ANCHOR_PRUNE") && atoi(getenv("MM2AMD_ANCHOR_PRUNE")) == 0);
+		// Where most reads give up -- accurate reads against a small reference: nearly every anchor is at the true locus and survives -- the filter pass is wasted:
+		// after a sub-batch that redid more than half of its reads the next 15 go unpruned, then one tries again.  (Not with the tests' knobs, which force give-ups.)
+		static const bool prune_adapt = !getenv("MM2AMD_PRUNE_BINS") && !getenv("MM2AMD_PRUNE_CAP");
+		const bool prune_can = prune_env && !P.rmq && !P.anchors_only && !has_pairs_ && !P.is_hpc && P.k < P.min_chain_score && !(P.flag & ref::F_HEAP_SORT) && !getenv("MM2AMD_SEED_DUMP");
+		const bool prune = prune_can && !(prune_adapt && prune_rest_.load() > 0 && prune_rest_.fetch_sub(1) > 0);
+		if (prune) {
+			ln.d_nkept.ensure(2 * n + 8); // the kept counts, the classes' redo counters (8 words), the classes' redo lists
+			B.n_kept = ln.d_nkept.p, B.redo_count = ln.d_nkept.p + n, B.redo_list = ln.d_nkept.p + n + 8;
+			static const int bins_env = getenv("MM2AMD_PRUNE_BINS") ? atoi(getenv("MM2AMD_PRUNE_BINS")) : 0, cap_env = getenv("MM2AMD_PRUNE_CAP") ? atoi(getenv("MM2AMD_PRUNE_CAP")) : 0;
+			B.prune_bins = bins_env, B.prune_cap = cap_env;
+		}
 		// the per-read anchor sort's launch classes (by anchors per read): the reads of a class are listed together
 		int n_class[kAnchorSortClasses] = { 0 }, class_first[kAnchorSortClasses + 1] = { 0 };
 		double a_class[kAnchorSortClasses] = { 0 };
@@ -390,6 +407,12 @@ public:
 		B.f = ln.d_f.p, B.p = ln.d_p.p, B.t = ln.d_t.p;
 		// 3. anchors: expand, sort, chain
 		kp.begin(st); launch_seed_expand(B, I_, P, st); kp.end(st, "seed_expand_kernel", 24.0 * n_a);
+		const bool dump_full = prune && P.chain_dump && chain_dump_path();
+		if (dump_full) { // diagnostics: the chain dump's IN block is the read's WHOLE sorted list (the reference's seed list) -- sorted unpruned into a buffer of its own first
+			SeedChainBuffers Bd = B;
+			Bd.anchors = ln.d_dump_anchors.ensure(n_a + 1), Bd.n_kept = nullptr, Bd.redo_list = Bd.redo_count = nullptr;
+			launch_anchor_sort(Bd, I_, P, ln.d_sort_list.p, n_class, a_class, st, nullptr);
+		}
 		launch_anchor_sort(B, I_, P, ln.d_sort_list.p, n_class, a_class, st, &kp);
 		if (getenv("MM2AMD_TIE_COUNT")) { // diagnostics: how many reads of this sub-batch had two anchors with the same x (the replayed ones)
 			std::vector<uint32_t> tf(n);
@@ -455,14 +478,14 @@ public:
 		}
 		make_pieces(B, ln, ln.h_pieces, n, [&](size_t i) { return (uint64_t)h_na[i]; }, P.rmq ? rmq_piece_len() : fill_piece_len(), st);
 		if (P.rmq) { kp.begin(st); launch_chain_rmq(B, P, st); kp.end(st, "chain_rmq_kernel", 32.0 * n_a); }
-		else { kp.begin(st); launch_chain_fill(B, P, st); kp.end(st, "chain_fill_kernel", 24.0 * n_a); }
+		else { kp.begin(st); launch_chain_fill(B, P, st); kp.end(st, "chain_fill_kernel", prune ? 0.0 : 24.0 * n_a); } // (pruned: per kept anchor, added below)
 		B.pieces = nullptr, B.n_pieces = 0;
 		// 4. chains: backtrack + compaction on the device, then only the chained anchors travel to the host
 		ln.d_bt_cursor.ensure(2), ln.d_bt_out_a.ensure(n_a + 1), ln.d_bt_out_u.ensure((P.min_cnt >= 2 ? n_a / 2 : n_a) + n + 1); // a chain has at least max(1, min_cnt) anchors (lchain.c:66)
 		ln.d_bt_nu.ensure(n), ln.d_bt_nv.ensure(n), ln.d_bt_aoff.ensure(n), ln.d_bt_uoff.ensure(n);
 		B.bt_cursor = ln.d_bt_cursor.p, B.bt_out_a = ln.d_bt_out_a.p, B.bt_out_u = ln.d_bt_out_u.p;
 		B.bt_nu = ln.d_bt_nu.p, B.bt_nv = ln.d_bt_nv.p, B.bt_aoff = ln.d_bt_aoff.p, B.bt_uoff = ln.d_bt_uoff.p;
-		kp.begin(st); launch_chain_backtrack(B, P, st); kp.end(st, "chain_backtrack_kernel", 8.0 * n_a);
+		kp.begin(st); launch_chain_backtrack(B, P, st); kp.end(st, "chain_backtrack_kernel", prune ? 0.0 : 8.0 * n_a);
 		unsigned long long *h_cur = ln.h_cursor.ensure(2);
 		int32_t *h_nu = ln.h_nu.ensure(n), *h_nv = ln.h_nv.ensure(n);
 		uint64_t *h_aoff = ln.h_aoff.ensure(n), *h_uoff = ln.h_uoff.ensure(n);
@@ -474,6 +497,8 @@ public:
 		HIP_CHECK(hipMemcpyAsync(h_aoff, ln.d_bt_aoff.p, n * 8, hipMemcpyDeviceToHost, st));
 		HIP_CHECK(hipMemcpyAsync(h_uoff, ln.d_bt_uoff.p, n * 8, hipMemcpyDeviceToHost, st));
 		if (h_tie) HIP_CHECK(hipMemcpyAsync(h_tie, ln.d_tie.p, n * 4, hipMemcpyDeviceToHost, st));
+		uint32_t *h_nkept = prune ? ln.h_nkept.ensure(2 * n + 8) : nullptr; // the kept counts and the redo counters; the redo lists only for the dump's KP lines
+		if (prune) HIP_CHECK(hipMemcpyAsync(h_nkept, ln.d_nkept.p, ((P.chain_dump && chain_dump_path() ? 2 * n : n) + 8) * 4, hipMemcpyDeviceToHost, st));
 		const bool lazy = P.lazy_chains != 0 && !P.anchors_only; // the chains stay on the device for align_regions()
 		ln.rg_lazy = lazy;
 		int32_t *h_span = nullptr;
@@ -484,6 +509,18 @@ public:
 		} else if (n_mp) HIP_CHECK(hipMemcpyAsync(hmp, ln.d_minipos.p, n_mp * 8, hipMemcpyDeviceToHost, st));
 		stream_wait(st);
 		Trace::get().add(lane_id, "gpu:expand..backtrack", tt, Trace::now()); tt = Trace::now();
+		if (prune) { // what the pruning did: the process-wide counters, and the bytes the three kernels moved for the anchors they were given
+			double kept_class[kAnchorSortClasses] = { 0 }, kept = 0;
+			unsigned long long n_redone = 0;
+			for (int c = 0; c + 1 < kAnchorSortClasses; ++c) n_redone += h_nkept[n + c];
+			for (size_t i = 0; i < n; ++i) if (h_na[i]) kept_class[anchor_sort_class(h_na[i], rid_bits_)] += h_nkept[i], kept += h_nkept[i];
+			size_t n_sorted = 0;
+			for (size_t i = 0; i < n; ++i) n_sorted += h_na[i] != 0;
+			if (prune_adapt && n_redone * 2 > n_sorted) prune_rest_.store(15);
+			prune_counters().n_in += n_a, prune_counters().n_kept += (unsigned long long)kept, prune_counters().n_redo += n_redone;
+			for (int c = 0; c + 1 < kAnchorSortClasses; ++c) if (kept_class[c] > 0) kp.add_bytes(kAnchorSortNames[c], 24.0 * kept_class[c]);
+			kp.add_bytes("chain_fill_kernel", 24.0 * kept), kp.add_bytes("chain_backtrack_kernel", 8.0 * kept);
+		}
 		const uint64_t n_v = h_cur[0], n_u = h_cur[1];
 		Anchor *ha = ln.h_anchors.ensure(n_v + 1);
 		uint64_t *hu = ln.h_u.ensure(n_u + 1);
@@ -506,14 +543,17 @@ public:
 		stream_wait(st);
 		if (cdump) { // the sorted anchors that went in and the first pass as the backtrack left it (with lazy chains the anchors are still on the device: copied here only)
 			std::vector<Anchor> all(n_a + 1), bt(lazy ? n_v + 1 : 0);
-			if (n_a) HIP_CHECK(hipMemcpyAsync(all.data(), ln.d_anchors.p, n_a * sizeof(Anchor), hipMemcpyDeviceToHost, st));
+			if (n_a) HIP_CHECK(hipMemcpyAsync(all.data(), dump_full ? ln.d_dump_anchors.p : ln.d_anchors.p, n_a * sizeof(Anchor), hipMemcpyDeviceToHost, st));
 			if (lazy && n_v) HIP_CHECK(hipMemcpyAsync(bt.data(), ln.d_bt_out_a.p, n_v * sizeof(Anchor), hipMemcpyDeviceToHost, st));
 			stream_wait(st);
 			const Anchor *chained = lazy ? bt.data() : ha;
+			std::vector<bool> redone(n, false); // (pruning: class c's redo list starts where the class's reads start in the sort's work list)
+			if (prune) for (int c = 0; c + 1 < kAnchorSortClasses; ++c) for (uint32_t q = 0; q < h_nkept[n + c]; ++q) redone[h_nkept[n + 8 + class_first[c] + q]] = true;
 			std::string txt;
 			for (size_t i = 0; i < n; ++i) {
 				ChainDumpBlock b = dump_block(i);
 				b.in = all.data() + a_off[i], b.n_in = (int64_t)(a_off[i + 1] - a_off[i]);
+				if (prune) b.n_kept = (int64_t)h_nkept[i], b.redone = redone[i]; // (KP line)
 				b.handed_back = h_tie && h_tie[i];
 				if (!b.handed_back) b.u = hu + h_uoff[i], b.n_u = h_nu[i], b.a = chained + h_aoff[i], b.n_a = h_nv[i];
 				chain_dump_format(txt, P, b);
@@ -544,8 +584,9 @@ public:
 
 	// The chaining kernels give a wavefront to a read.  A read with far more anchors than the others (it crosses a multi-copy element of the reference) makes the whole
 	// launch wait for its wavefront, so when a read has more than `len` anchors the launch gets a work list instead: every read's ceil(anchors / len) pieces (seed_chain.hip:
-	// chain_piece_bounds moves the cuts to cluster heads, where the sequential rules restart), the reads with several pieces first.  Launches without such a read --
-	// every launch of the uniform benchmark -- keep the plain read-per-wavefront grid.  MM2AMD_CHAIN_PIECE / MM2AMD_RMQ_PIECE: the piece lengths (tests set small ones; 0 = never cut).
+	// chain_piece_bounds moves the cuts to cluster heads, where the sequential rules restart), the reads with several pieces first.  Launches without such a read
+	// keep the plain read-per-wavefront grid; the benchmark's reads, ~7 k anchors each against a cut at 4 096, do get lists.  The list is made from the counts BEFORE
+	// pruning (the kept counts never come to the host in time): a piece that starts beyond a read's kept anchors returns at once.  MM2AMD_CHAIN_PIECE / MM2AMD_RMQ_PIECE: the piece lengths (tests set small ones; 0 = never cut).
 	static int fill_piece_len() { const char *e = getenv("MM2AMD_CHAIN_PIECE"); return e ? atoi(e) : 4096; }
 	static int rmq_piece_len() { const char *e = getenv("MM2AMD_RMQ_PIECE"); return e ? atoi(e) : 512; }
 	template <class Count>
@@ -603,6 +644,7 @@ public:
 		const uint64_t n_a2 = h_off[n2];
 		SeedChainBuffers B2 = ln.B;
 		B2.n_reads = (int)n2, B2.seq_off = nullptr, B2.mz_cnt = nullptr, B2.unit_first = nullptr;
+		B2.n_kept = nullptr, B2.redo_list = B2.redo_count = nullptr; // (the re-chain takes every chained anchor)
 		ln.d_lj_src.ensure(n2 + 1), ln.d_lj_out_a.ensure(n_a2 + 1);
 		HIP_CHECK(hipMemcpyAsync(ln.d_a_off.p, h_off, (n2 + 1) * 8, hipMemcpyHostToDevice, st));
 		HIP_CHECK(hipMemcpyAsync(ln.d_lj_src.p, h_src, n2 * 8, hipMemcpyHostToDevice, st));
@@ -1046,6 +1088,7 @@ private:
 	hipStream_t stream_ = nullptr;
 	int n_threads_ = 1, n_cu_ = 256, n_lanes_ = 1, rid_bits_ = 1, dev_ = 0, replica_ = 0;
 	std::atomic<int> active_lanes_{1};
+	std::atomic<int> prune_rest_{0}; // sub-batches that still go unpruned because a recent one sent most of its reads to the unpruned sort anyway (seed_chain)
 	DevIndex I_{};
 	DeviceIndexTables own_;
 	DeviceIndexTables *T_ = nullptr;

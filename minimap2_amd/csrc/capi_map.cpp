@@ -33,7 +33,7 @@ int capi_fail(int code, const std::string &msg);
 
 using namespace mm2amd;
 
-extern "C" long long mm2amd_alloc_counter(int which); // device allocations, pinned allocations, nanoseconds spent in them; 3..6: the banded gap fill's windows tried in 128 / 256 diagonals, widened, recomputed as rectangles (process-wide)
+extern "C" long long mm2amd_alloc_counter(int which); // device allocations, pinned allocations, nanoseconds spent in them; 3..6: the banded gap fill's windows tried in 128 / 256 diagonals, widened, recomputed as rectangles; 13..15: anchors before / after pruning, reads sorted unpruned after all (process-wide)
 
 namespace {
 // Where the results of one mapper fragment go: reads o .. o+n_out-1 of the caller's arrays; flip_len[j] >= 0 when read o+j was
@@ -775,7 +775,8 @@ int mm2amd_last_stats(double *v, int n)
 	                     (double)s.n_region_reads_dev, (double)s.n_region_reads_host,
 	                     (double)mm2amd_alloc_counter(3), (double)mm2amd_alloc_counter(4), (double)mm2amd_alloc_counter(5), (double)mm2amd_alloc_counter(6),
 	                     (double)mm2amd_alloc_counter(7), (double)mm2amd_alloc_counter(8), (double)mm2amd_alloc_counter(9), (double)mm2amd_alloc_counter(10),
-	                     (double)mm2amd_alloc_counter(11), (double)mm2amd_alloc_counter(12) }; // (the arenas behind the work buffers: bytes held in chunks, device / pinned; bytes handed out of them) // (process CPU seconds while a lane was in the stage: lanes overlap, so these attribute, they do not add up)
+	                     (double)mm2amd_alloc_counter(11), (double)mm2amd_alloc_counter(12),
+	                     (double)mm2amd_alloc_counter(13), (double)mm2amd_alloc_counter(14), (double)mm2amd_alloc_counter(15) }; // (the arenas behind the work buffers: bytes held in chunks, device / pinned; bytes handed out of them) // (process CPU seconds while a lane was in the stage: lanes overlap, so these attribute, they do not add up)
 	int k = 0;
 	for (; k < n && k < (int)(sizeof a / sizeof a[0]); ++k) v[k] = a[k];
 	return k;

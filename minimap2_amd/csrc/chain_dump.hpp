@@ -8,6 +8,8 @@
 //   PR  gap_ref gap_qry bw max_chain_skip max_chain_iter min_cnt min_chain_score chn_pen_gap chn_pen_skip is_cdna n_seg rmq rmq_inner_dist
 //       rmq_size_cap bw_long mid_occ      the parameters of the call (the two penalties as %a: the floats round-trip)
 //   IN  n  x y x y ...                    the sorted anchors that entered the pass ("IN -": not recorded -- the re-chain's input is the sorted first pass)
+//   KP  n  redone                         only with MM2AMD_CHAIN_DUMP_KEPT=1, and only where isolated anchors were pruned before the sort (seed_chain.hip:
+//                                         anchor_sort_prune_kernel): how many of the IN anchors the chaining kernels were given; 1 = the read was sorted unpruned after all
 //   U   n  u u ...                        the chains, in order: score << 32 | anchors
 //   A   n  x y x y ...                    the chained anchors, chain by chain
 //   END
@@ -29,6 +31,8 @@ struct ChainDumpBlock {
 	bool host = false, handed_back = false;
 	const Anchor *in = nullptr; // null: not recorded
 	int64_t n_in = 0;
+	int64_t n_kept = -1;        // >= 0: the call pruned isolated anchors, and this many of the read's went on to the chaining
+	bool redone = false;        // ... after the unpruned sort took the read over (duplicated keys, too many survivors): n_kept == n_in
 	const uint64_t *u = nullptr;
 	int32_t n_u = 0;
 	const Anchor *a = nullptr;
@@ -61,6 +65,8 @@ inline void chain_dump_format(std::string &s, const SeedChainParams &P, const Ch
 	s += buf;
 	if (b.in) chain_dump_words(s, "IN", b.n_in, (const uint64_t *)b.in, 2 * b.n_in);
 	else s += "IN\t-\n";
+	static const bool kept_lines = getenv("MM2AMD_CHAIN_DUMP_KEPT") != nullptr;
+	if (kept_lines && b.n_kept >= 0) { snprintf(buf, sizeof(buf), "KP\t%lld\t%d\n", (long long)b.n_kept, b.redone ? 1 : 0); s += buf; }
 	int64_t n_a = 0;
 	for (int32_t k = 0; k < b.n_u; ++k) n_a += (int32_t)b.u[k];
 	if (n_a != b.n_a) { snprintf(buf, sizeof(buf), "ERR\tchains of %lld anchors, %lld anchors\n", (long long)n_a, (long long)b.n_a); s += buf; n_a = n_a < b.n_a ? n_a : b.n_a; }

@@ -86,6 +86,9 @@ inline AllocStats &alloc_stats() { static AllocStats s; return s; }
 // band, computed again as the full rectangle
 struct BandCounters { std::atomic<unsigned long long> n_band1{0}, n_band2{0}, n_band4{0}, n_widened{0}, n_retried{0}, n_retried_big{0}; };
 inline BandCounters &band_counters() { static BandCounters s; return s; }
+// anchor pruning since the process started (backend_hip.cpp): anchors of the calls that pruned, what the chaining kernels were given of them, reads sorted unpruned after all
+struct PruneCounters { std::atomic<unsigned long long> n_in{0}, n_kept{0}, n_redo{0}; };
+inline PruneCounters &prune_counters() { static PruneCounters s; return s; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Arenas behind DevBuf / PinBuf (round 6).  The work buffers of the lanes are grow-only vectors that find their sizes during the first batches: ~550 hipMalloc and

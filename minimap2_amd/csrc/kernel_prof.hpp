@@ -33,6 +33,8 @@ public:
 	}
 	// a count that goes with a kernel but is no launch of its own (the banded DP kernel: the cells it computed, beside the cells of the rectangles it replaced)
 	void add_units(const char *name, double units) { if (enabled_flag()) stats_[name].units += units; }
+	// bytes of a launch that are known only after it ran (the anchor pruning: what a kernel moved depends on the kept count)
+	void add_bytes(const char *name, double alg_bytes) { if (enabled_flag()) stats_[name].alg_bytes += alg_bytes; }
 	// call after the stream has been synchronised
 	void collect()
 	{

@@ -1250,7 +1250,7 @@ __device__ __forceinline__ void tie_exact_replay(S s, int32_t n, const uint64_t 
 }
 
 template <int THREADS, int ROUNDS, bool IN_LDS>
-__global__ void __launch_bounds__(THREADS, (THREADS == 1024 && IN_LDS && ROUNDS <= 7) ? 8 : 4) /* (waves per SIMD) the 7 k class: two workgroups of 1024 per CU, 64 VGPRs */ anchor_sort_kernel(SeedChainBuffers B, const uint32_t *list, int heap_sort)
+__global__ void __launch_bounds__(THREADS, (THREADS == 1024 && IN_LDS && ROUNDS <= 7) ? 8 : 4) /* (waves per SIMD) the 7 k class: two workgroups of 1024 per CU, 64 VGPRs */ anchor_sort_kernel(SeedChainBuffers B, const uint32_t *list, const uint32_t *count, int heap_sort)
 {
 	MM2_DYN_LDS(uint64_t, as_lds); // IN_LDS: the read's packed elements
 	__shared__ uint32_t tab[(THREADS / 64) * 256]; // the radix passes' per-wave digit counters; afterwards the replay's three 256-entry tables
@@ -1260,12 +1260,17 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 1024 && IN_LDS && ROUNDS 
 	__shared__ uint32_t n_tied_s;
 	uint32_t *const cnt = tab, *const head = tab + 256, *const start = tab + 512;
 	const int32_t tid = (int32_t)threadIdx.x;
-	const int r = (int)list[blockIdx.x];
+	// a workgroup per read of the list; with `count` (the pruning launches' redo list: its length is known on the device only) the grid walks the list
+	const uint32_t n_list = count ? *count : gridDim.x;
+	for (uint32_t li = blockIdx.x; li < n_list; li += gridDim.x) {
+	if (li != blockIdx.x) __syncthreads(); // (the previous read's last pass over the shared arrays)
+	const int r = (int)list[li];
 	const uint64_t ao = B.a_off[r];
 	const int32_t n = (int32_t)(B.a_off[r + 1] - ao);
 	const uint64_t *kin = B.sort_key_in + ao, *vin = B.sort_val_in + ao;
 	Anchor *out = B.anchors + ao;
-	if (n == 0) return;
+	if (n == 0) continue;
+	if (B.n_kept && tid == 0) B.n_kept[r] = (uint32_t)n; // nothing is pruned here
 	auto run = [&](auto s, TieFrame *stack, int stack_cap) {
 		// 1. (key, original index) pairs, sorted by (key, index)
 		for (int32_t i = tid; i < n; i += THREADS) s.set(i, kin[i], (uint32_t)i);
@@ -1313,6 +1318,114 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 1024 && IN_LDS && ROUNDS 
 	else { // the sorted-pair arrays are free until the backtrack: keys, then indices and the frame stack in the value array
 		uint32_t *I = (uint32_t *)(B.sort_val_out + ao);
 		run(SplitStore{B.sort_key_out + ao, I, B.rid_bits}, (TieFrame *)(I + n), (int)((size_t)n * 4 / sizeof(TieFrame)));
+	}
+	}
+}
+
+// The look-back window of the chaining DP for read r (lchain.c:172; map.c:262-271 and the bw clamps of mg_lchain_dp): an anchor sees the anchors of its
+// strand and target at most *max_dist_x upstream.  ONE function for chain_fill_kernel and for the pruning below, whose exactness rests on the two agreeing.
+__device__ __forceinline__ void chain_window(const SeedChainBuffers &B, const SeedChainParams &P, int r, int32_t *max_dist_x, int32_t *max_dist_y)
+{
+	chain_gaps(P, (int)(B.seq_off[r + 1] - B.seq_off[r]), max_dist_x, max_dist_y);
+	if (*max_dist_x < P.bw) *max_dist_x = P.bw;
+	if (*max_dist_y < P.bw && !P.is_cdna) *max_dist_y = P.bw;
+}
+
+// The sort of an LDS class with the isolated anchors taken out first.  Against a large reference most of a read's anchors are random single hits with
+// no anchor of the same strand and target within the chaining window on EITHER side.  Such an anchor has an empty look-back window (f = span, p = -1),
+// lies in no other anchor's window, resets the fill's running state the way the next anchor -- out of range as well -- resets it anyway, and with
+// span < min_chain_score never becomes a chain end: the chains are the same without it, so it need not be sorted, written, filled or backtracked.
+//   1. mark     every key's bin (a hash of key >> s, 2^s >= max_dist + 1) gets a two-bit saturating count in an LDS table: none / one / several;
+//   2. test     an anchor survives if its bin holds several or a neighbouring bin (key >> s one less or one more) holds any: two anchors in range of
+//               each other share a bin or sit in neighbouring ones, so collisions and contig boundaries only ever keep more; survivors are packed into LDS;
+//   3. sort     lds_radix_sort over the survivors;
+//   4. prune    a sorted survivor whose two neighbours are both out of range goes too -- exact among ALL anchors, since step 2 dropped only anchors in
+//               range of nobody;
+//   5. write    the rest, densely from a_off[r]; n_kept[r] is their number.
+// The reference's tie order depends on the whole unsorted array, so a read with a duplicated key (both copies always survive: they are 0 apart) goes on
+// its class's redo list, as does a read whose survivors outgrow the capacity; the class's unpruned kernel sorts those from the untouched (key, value) arrays afterwards.
+// LDS: the class's CAP words as before -- 3/8 of them hold survivors, 5/8 the table (20 bins per anchor of a full read: about 15 % of the isolated anchors
+// of a full read pass step 2 by collision).
+template <int THREADS, int ROUNDS, int CAP>
+__global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 8 : 4) anchor_sort_prune_kernel(SeedChainBuffers B, SeedChainParams P, const uint32_t *list, uint32_t *redo_list, uint32_t *redo_count)
+{
+	constexpr int S_MAX = CAP * 3 / 8, NW = THREADS / 64;
+	constexpr uint32_t W_MAX = (uint32_t)(CAP - S_MAX) * 2u; // 32-bit words of the table, 16 bins each
+	static_assert(S_MAX <= THREADS * ROUNDS, "a wavefront's segment of the survivors fits its rounds");
+	MM2_DYN_LDS(uint64_t, as_lds); // CAP words: S_MAX packed survivors, then the presence table
+	__shared__ uint32_t tab[NW * 256];
+	__shared__ uint32_t dig_tot[256], wave_tot[NW];
+	__shared__ uint32_t n_surv_s, redo_s;
+	const int32_t tid = (int32_t)threadIdx.x;
+	const int lane = tid & 63, w = tid >> 6;
+	const int r = (int)list[blockIdx.x];
+	const uint64_t ao = B.a_off[r];
+	const int32_t n = (int32_t)(B.a_off[r + 1] - ao);
+	const uint64_t *kin = B.sort_key_in + ao, *vin = B.sort_val_in + ao;
+	Anchor *out = B.anchors + ao;
+	if (n == 0) return;
+	int32_t max_dist, max_dist_y;
+	chain_window(B, P, r, &max_dist, &max_dist_y);
+	int s = 0;
+	while (s < 31 && (1u << s) < (uint32_t)max_dist + 1u) ++s;
+	const uint32_t s_cap = B.prune_cap > 0 && B.prune_cap < S_MAX ? (uint32_t)B.prune_cap : (uint32_t)S_MAX;
+	const uint32_t bins = B.prune_bins > 0 && (uint32_t)B.prune_bins < W_MAX * 16u ? (uint32_t)B.prune_bins : W_MAX * 16u;
+	uint32_t *const bt = (uint32_t *)(as_lds + S_MAX);
+	auto bin_of = [&](uint64_t q) { return (uint32_t)((uint64_t)(((uint32_t)q ^ (uint32_t)(q >> 32) * 0x85ebca6bu) * 0x9e3779b1u) * bins >> 32); };
+	for (uint32_t i = (uint32_t)tid; i < (bins + 15u) / 16u; i += THREADS) bt[i] = 0;
+	if (tid == 0) n_surv_s = 0, redo_s = 0;
+	__syncthreads();
+	for (int32_t i = tid; i < n; i += THREADS) { // 1. mark
+		const uint32_t b = bin_of(kin[i] >> s), sh = (b & 15u) * 2u;
+		const uint32_t old = atomicOr(&bt[b >> 4], 1u << sh);
+		if (old >> sh & 1u) atomicOr(&bt[b >> 4], 2u << sh);
+	}
+	__syncthreads();
+	for (int32_t base = 0; base < n; base += THREADS) { // 2. test and compact (every lane takes every turn: the ballot)
+		const int32_t i = base + tid;
+		uint64_t key = 0;
+		bool keep = false;
+		if (i < n) {
+			key = kin[i];
+			const uint64_t q = key >> s;
+			const uint32_t b = bin_of(q), lo = bin_of(q - 1), hi = bin_of(q + 1);
+			keep = (bt[b >> 4] >> ((b & 15u) * 2u) & 2u) != 0 || (bt[lo >> 4] >> ((lo & 15u) * 2u) & 1u) != 0 || (bt[hi >> 4] >> ((hi & 15u) * 2u) & 1u) != 0;
+		}
+		const unsigned long long m = __ballot(keep);
+		uint32_t first = 0;
+		if (lane == 0 && m) first = atomicAdd(&n_surv_s, (uint32_t)__popcll(m));
+		first = (uint32_t)__shfl((int)first, 0, 64);
+		if (keep) { const uint32_t slot = first + (uint32_t)popc_below(m, lane); if (slot < s_cap) as_lds[slot] = key << AS_IDX_BITS | (uint64_t)(uint32_t)i; }
+	}
+	__syncthreads();
+	const uint32_t n_surv = n_surv_s;
+	if (n_surv > s_cap) { if (tid == 0) redo_list[atomicAdd(redo_count, 1u)] = (uint32_t)r; return; }
+	if (n_surv == 0) { if (tid == 0) B.n_kept[r] = 0; return; }
+	const int32_t m = (int32_t)n_surv;
+	lds_radix_sort<THREADS, ROUNDS>(as_lds, m, 33 + B.rid_bits, tab, dig_tot); // 3. (ends on a barrier)
+	auto near = [&](uint64_t a, uint64_t b) { return a >> 32 == b >> 32 && b - a <= (uint64_t)(int64_t)max_dist; }; // compact keys, a <= b: same strand and target, within the window
+	uint32_t n_out = 0;
+	for (int32_t base = 0; base < m; base += THREADS) { // 4. + 5.
+		const int32_t i = base + tid;
+		uint64_t e = 0, k = 0;
+		bool keep = false;
+		if (i < m) {
+			e = as_lds[i], k = e >> AS_IDX_BITS;
+			if (i > 0) { const uint64_t kp = as_lds[i - 1] >> AS_IDX_BITS; keep = near(kp, k); if (kp == k) redo_s = 1u; }
+			if (i + 1 < m) keep = keep || near(k, as_lds[i + 1] >> AS_IDX_BITS);
+		}
+		const unsigned long long mk = __ballot(keep);
+		if (lane == 0) wave_tot[w] = (uint32_t)__popcll(mk);
+		__syncthreads();
+		uint32_t before = 0, total = 0;
+		for (int w2 = 0; w2 < NW; ++w2) { const uint32_t t = wave_tot[w2]; if (w2 < w) before += t; total += t; }
+		if (keep) { Anchor a; a.x = key_to_x(k, B.rid_bits), a.y = vin[(uint32_t)e & ((1u << AS_IDX_BITS) - 1u)]; out[n_out + before + (uint32_t)popc_below(mk, lane)] = a; }
+		n_out += total;
+		__syncthreads();
+	}
+	if (tid == 0) {
+		if (redo_s) redo_list[atomicAdd(redo_count, 1u)] = (uint32_t)r; // (what was written is written again)
+		else B.n_kept[r] = n_out;
 	}
 }
 
@@ -1417,6 +1530,7 @@ __global__ void __launch_bounds__(64) anchor_heap_order_kernel(SeedChainBuffers 
 // anchors per read an LDS class holds (the last class sorts on global scratch with the comparison network) and the workgroup that sorts
 // it (a 10 kb ONT read has ~7 k anchors against a 3 Gb reference: 56 KB of elements + 20 KB of tables, two workgroups of 1024 threads per CU)
 const int kAnchorSortCap[kAnchorSortClasses] = { 1024, 2048, 4096, 7168, AS_LDS_MAX, 0 };
+const char *const kAnchorSortNames[kAnchorSortClasses] = { "anchor_sort_kernel[n1k]", "anchor_sort_kernel[n2k]", "anchor_sort_kernel[n4k]", "anchor_sort_kernel[n7k]", "anchor_sort_kernel[n10k]", "anchor_sort_kernel[global]" };
 // workgroups: 256, 256, 512, 1024, 1024 threads (4, 8, 8, 7, 10 rounds of 64 elements per wave); 1024 for the global class
 
 int anchor_sort_class(uint64_t n_anchors, int rid_bits)
@@ -1435,7 +1549,7 @@ void launch_anchor_sort(const SeedChainBuffers &B, const DevIndex &I, const Seed
 	KernelProfiler none;
 	if (!kp) kp = &none;
 	HIP_CHECK(hipMemsetAsync(B.tie_flag, 0, (size_t)B.n_reads * 4, s));
-	static const char *kNames[kAnchorSortClasses] = { "anchor_sort_kernel[n1k]", "anchor_sort_kernel[n2k]", "anchor_sort_kernel[n4k]", "anchor_sort_kernel[n7k]", "anchor_sort_kernel[n10k]", "anchor_sort_kernel[global]" };
+	const char *const *kNames = kAnchorSortNames;
 	// (function attributes are per device and lane drivers of several replicas call this concurrently: set it before every launch that needs it,
 	// as ksw_extd2.hip does -- a table write in the runtime, microseconds)
 	if (n_class[4] > 0) HIP_CHECK(hipFuncSetAttribute((const void *)anchor_sort_kernel<1024, 10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, AS_LDS_MAX * 8));
@@ -1446,22 +1560,57 @@ void launch_anchor_sort(const SeedChainBuffers &B, const DevIndex &I, const Seed
 	const bool no_split = getenv("MM2AMD_TIE_NO_STRAND_SPLIT") != nullptr;           // A/B checks: one workgroup per read replays both strands' halves
 	const int heap = ((P.flag & ref::F_HEAP_SORT) || no_replay ? 1 : 0) | (walk_only ? 2 : 0) | (replay_inline ? 0 : 4) | (no_tape ? 8 : 0) | (no_split ? 16 : 0);
 	if (heap & 4) HIP_CHECK(hipMemsetAsync(B.tie_count, 0, 4, s));
+	const bool prune = B.n_kept != nullptr; // (the backend decides: launch_anchor_sort's callers set n_kept only where dropping isolated anchors is exact)
+	if (prune) {
+		HIP_CHECK(hipMemsetAsync(B.n_kept, 0, (size_t)B.n_reads * 4, s));
+		HIP_CHECK(hipMemsetAsync(B.redo_count, 0, 4 * kAnchorSortClasses, s));
+		if (n_class[4] > 0) HIP_CHECK(hipFuncSetAttribute((const void *)anchor_sort_prune_kernel<1024, 4, AS_LDS_MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, AS_LDS_MAX * 8));
+	}
 	int first = 0;
 	for (int c = 0; c < kAnchorSortClasses; first += n_class[c], ++c) {
 		if (n_class[c] == 0) continue;
 		kp->begin(s);
 		const size_t lds = (size_t)kAnchorSortCap[c] * 8;
 		const dim3 grid(n_class[c]);
-		if (c == 0) hipLaunchKernelGGL((anchor_sort_kernel<256, 4, true>), grid, dim3(256), lds, s, B, d_list + first, heap);
-		else if (c == 1) hipLaunchKernelGGL((anchor_sort_kernel<256, 8, true>), grid, dim3(256), lds, s, B, d_list + first, heap);
-		else if (c == 2) hipLaunchKernelGGL((anchor_sort_kernel<512, 8, true>), grid, dim3(512), lds, s, B, d_list + first, heap);
-		else if (c == 3) hipLaunchKernelGGL((anchor_sort_kernel<1024, 7, true>), grid, dim3(1024), lds, s, B, d_list + first, heap);
-		else if (c == 4) hipLaunchKernelGGL((anchor_sort_kernel<1024, 10, true>), grid, dim3(1024), lds, s, B, d_list + first, heap);
-		else hipLaunchKernelGGL((anchor_sort_kernel<1024, 1, false>), grid, dim3(1024), 0, s, B, d_list + first, heap);
+		const uint32_t *none_counted = nullptr;
+		if (prune && c + 1 < kAnchorSortClasses) { // the same LDS per workgroup as the unpruned class; the survivors' sort takes 2 .. 4 rounds instead of 4 .. 10
+			if (c == 0) hipLaunchKernelGGL((anchor_sort_prune_kernel<256, 2, 1024>), grid, dim3(256), lds, s, B, P, d_list + first, B.redo_list + first, B.redo_count + c);
+			else if (c == 1) hipLaunchKernelGGL((anchor_sort_prune_kernel<256, 3, 2048>), grid, dim3(256), lds, s, B, P, d_list + first, B.redo_list + first, B.redo_count + c);
+			else if (c == 2) hipLaunchKernelGGL((anchor_sort_prune_kernel<512, 3, 4096>), grid, dim3(512), lds, s, B, P, d_list + first, B.redo_list + first, B.redo_count + c);
+			else if (c == 3) hipLaunchKernelGGL((anchor_sort_prune_kernel<1024, 3, 7168>), grid, dim3(1024), lds, s, B, P, d_list + first, B.redo_list + first, B.redo_count + c);
+			else hipLaunchKernelGGL((anchor_sort_prune_kernel<1024, 4, AS_LDS_MAX>), grid, dim3(1024), lds, s, B, P, d_list + first, B.redo_list + first, B.redo_count + c);
+			kp->end(s, kNames[c], 16.0 * anchors_in_class[c]); // the keys, twice; the backend adds 24 B per KEPT anchor (its y in, the anchor out) once the counts are back
+			HIP_CHECK(hipGetLastError());
+			continue;
+		}
+		if (c == 0) hipLaunchKernelGGL((anchor_sort_kernel<256, 4, true>), grid, dim3(256), lds, s, B, d_list + first, none_counted, heap);
+		else if (c == 1) hipLaunchKernelGGL((anchor_sort_kernel<256, 8, true>), grid, dim3(256), lds, s, B, d_list + first, none_counted, heap);
+		else if (c == 2) hipLaunchKernelGGL((anchor_sort_kernel<512, 8, true>), grid, dim3(512), lds, s, B, d_list + first, none_counted, heap);
+		else if (c == 3) hipLaunchKernelGGL((anchor_sort_kernel<1024, 7, true>), grid, dim3(1024), lds, s, B, d_list + first, none_counted, heap);
+		else if (c == 4) hipLaunchKernelGGL((anchor_sort_kernel<1024, 10, true>), grid, dim3(1024), lds, s, B, d_list + first, none_counted, heap);
+		else hipLaunchKernelGGL((anchor_sort_kernel<1024, 1, false>), grid, dim3(1024), 0, s, B, d_list + first, none_counted, heap);
 		kp->end(s, kNames[c], 32.0 * anchors_in_class[c]); // 16 B per anchor in, 16 B out (nothing else leaves LDS)
 		HIP_CHECK(hipGetLastError());
 	}
 	const int n_lds = n_class[0] + n_class[1] + n_class[2] + n_class[3] + n_class[4];
+	if (prune && n_lds > 0) { // the reads the pruning workgroups gave up, class by class with the class's own unpruned workgroup; how many is known on the device only
+		kp->begin(s);
+		if (n_class[4] > 0) HIP_CHECK(hipFuncSetAttribute((const void *)anchor_sort_kernel<1024, 10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, AS_LDS_MAX * 8));
+		int at = 0;
+		for (int c = 0; c + 1 < kAnchorSortClasses; at += n_class[c], ++c) {
+			if (n_class[c] == 0) continue;
+			const size_t lds = (size_t)kAnchorSortCap[c] * 8;
+			const dim3 grid(std::min(n_class[c], 1024)); // (a bound: the workgroups walk the list)
+			const uint32_t *rl = B.redo_list + at, *rc = B.redo_count + c;
+			if (c == 0) hipLaunchKernelGGL((anchor_sort_kernel<256, 4, true>), grid, dim3(256), lds, s, B, rl, rc, heap);
+			else if (c == 1) hipLaunchKernelGGL((anchor_sort_kernel<256, 8, true>), grid, dim3(256), lds, s, B, rl, rc, heap);
+			else if (c == 2) hipLaunchKernelGGL((anchor_sort_kernel<512, 8, true>), grid, dim3(512), lds, s, B, rl, rc, heap);
+			else if (c == 3) hipLaunchKernelGGL((anchor_sort_kernel<1024, 7, true>), grid, dim3(1024), lds, s, B, rl, rc, heap);
+			else hipLaunchKernelGGL((anchor_sort_kernel<1024, 10, true>), grid, dim3(1024), lds, s, B, rl, rc, heap);
+			HIP_CHECK(hipGetLastError());
+		}
+		kp->end(s, "anchor_sort_kernel[redo]", 0.0);
+	}
 	if ((heap & 4) && !(heap & 1) && n_lds > 0) {
 		kp->begin(s);
 		HIP_CHECK(hipFuncSetAttribute((const void *)anchor_sort_ties_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AST_LDS_BYTES));
@@ -1571,15 +1720,13 @@ __global__ void __launch_bounds__(256) chain_fill_kernel(SeedChainBuffers B, See
 	uint64_t *const rx = s_x[wave], *const ry = s_y[wave];
 	int32_t *const rf = s_f[wave], *const rp = s_p[wave], *const rt = s_t[wave];
 	const Anchor *a = B.anchors + B.a_off[r];
-	const int64_t n_all = (int64_t)(B.a_off[r + 1] - B.a_off[r]);
+	const int64_t n_all = B.n_kept ? (int64_t)B.n_kept[r] : (int64_t)(B.a_off[r + 1] - B.a_off[r]); // (pruned: the host's piece list was made from the counts before; a piece beyond the kept anchors is empty)
 	int32_t *f = B.f + B.a_off[r], *p = B.p + B.a_off[r], *t = B.t + B.a_off[r];
 	int32_t max_dist_x, max_dist_y;
-	chain_gaps(P, (int)(B.seq_off[r + 1] - B.seq_off[r]), &max_dist_x, &max_dist_y);
+	chain_window(B, P, r, &max_dist_x, &max_dist_y);
 	max_dist_x = __builtin_amdgcn_readfirstlane(max_dist_x), max_dist_y = __builtin_amdgcn_readfirstlane(max_dist_y); // one read per wavefront: keep the limits in scalar registers, as when they were launch constants
 	const int n_seg = PAIRS ? B.unit_first[r + 1] - B.unit_first[r] : 1;
 	const int32_t bw = P.bw;
-	if (max_dist_x < bw) max_dist_x = bw;
-	if (max_dist_y < bw && !P.is_cdna) max_dist_y = bw;
 	int64_t lo = 0, n = n_all; // the anchors [lo, n) of the read are this wavefront's
 	if (B.pieces) chain_piece_bounds(a, n_all, (int64_t)B.pieces[2 * w + 1], (int64_t)B.piece_len, max_dist_x, lane, &lo, &n);
 	if (lo >= n) return;
@@ -2228,7 +2375,7 @@ __global__ void __launch_bounds__(64) chain_backtrack_kernel(SeedChainBuffers B,
 	const int lane = threadIdx.x;
 	const int r = blockIdx.x;
 	const uint64_t ao = B.a_off[r];
-	const int32_t n = (int32_t)(B.a_off[r + 1] - ao);
+	const int32_t n = B.n_kept ? (int32_t)B.n_kept[r] : (int32_t)(B.a_off[r + 1] - ao);
 	const Anchor *a = B.anchors + ao;
 	const int32_t *f = B.f + ao, *p = B.p + ao;
 	int32_t *t = B.t + ao;

@@ -51,6 +51,12 @@ struct SeedChainBuffers {     // all device pointers; per-read slices addressed 
 	uint32_t *tie_flag;       // n_reads: set when a read has two anchors with equal x
 	uint32_t *tie_list, *tie_count; // those reads (of the LDS classes), in the order their sorting workgroups found out; how many: anchor_sort_ties_kernel's work list
 	int rid_bits;             // bits needed for a reference sequence id in the compact sort key
+	// anchor pruning (seed_chain.hip: anchor_sort_prune_kernel; null / 0: off, every consumer takes a_off[r + 1] - a_off[r]): the sorted anchors the read
+	// keeps, written densely from a_off[r]; the reads the pruning workgroups left to the unpruned sort (duplicated keys, too many survivors), class by class
+	// (class c's from the offset its reads have in the sort's work list), and how many per class (kAnchorSortClasses counters)
+	uint32_t *n_kept = nullptr;
+	uint32_t *redo_list = nullptr, *redo_count = nullptr;
+	int prune_bins = 0, prune_cap = 0; // tests: upper limits on the presence table's bins / the survivor capacity (0: what the launch class holds)
 	uint64_t *mini_pos;
 	int32_t *f, *p, *t;       // chaining DP arrays, indexed like anchors
 	// the chaining kernels' work list (null: one wavefront per read): (read, piece number) pairs, a piece = piece_len anchors moved to the next cluster
@@ -77,7 +83,9 @@ class KernelProfiler;
 // the per-read anchor sort's launch classes (by anchors per read; the last one sorts on global scratch): `list` holds the reads grouped
 // by class, n_class[c] of them in class c, carrying anchors_in_class[c] anchors
 constexpr int kAnchorSortClasses = 6;
+extern const char *const kAnchorSortNames[kAnchorSortClasses]; // the classes' names in the kernel profile
 int anchor_sort_class(uint64_t n_anchors, int rid_bits);
+// B.n_kept set: the LDS classes prune isolated anchors (anchor_sort_prune_kernel) and B.n_kept[r] is what every later kernel takes as read r's count
 void launch_anchor_sort(const SeedChainBuffers &B, const DevIndex &I, const SeedChainParams &P, const uint32_t *d_list, const int *n_class, const double *anchors_in_class, void *stream,
                         KernelProfiler *kp);
 void launch_chain_fill(const SeedChainBuffers &B, const SeedChainParams &P, void *stream);
