@@ -87,8 +87,12 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
  *   MM2AMD_TXT_CS       the short cs string, identity runs as ":n" (write_cs_ds_core with no_iden = 1 and is_ds = 0, format.c:171-254)
  *   MM2AMD_TXT_CS_LONG  the long cs string, identity runs as "=ACGT" (no_iden = 0)
  *   MM2AMD_TXT_MD       the MD string (write_MD_core, format.c:302-331)
- * without the "cs:Z:" / "MD:Z:" tag in front, as mm_gen_cs / mm_gen_MD (format.c:364-395) return them.  The ds string is not produced here.
- * A job is one alignment: the aligned stretches as nt4 codes (0-3, 4 = N) and its CIGAR.  For cs / MD the operations must be M, I, D, N, = or
+ *   MM2AMD_TXT_DS       the short ds string: cs with, for every insertion and deletion, brackets around the bases by which the gap can be
+ *                       shifted without changing the alignment, as in "+[a]" or "+[t]aca[gat]" (write_cs_ds_core with is_ds = 1 and
+ *                       no_iden = 1, and write_indel_ds, format.c:142-254).  The shifts stop at the ends of the aligned stretches.
+ *   MM2AMD_TXT_DS_LONG  the long ds string (no_iden = 0)
+ * without the "cs:Z:" / "ds:Z:" / "MD:Z:" tag in front, as mm_gen_cs / mm_gen_ds / mm_gen_MD (format.c:364-395) return them.
+ * A job is one alignment: the aligned stretches as nt4 codes (0-3, 4 = N) and its CIGAR.  For cs / ds / MD the operations must be M, I, D, N, = or
  * X, none of length 0, no N shorter than 2, and they must cover exactly qlen and tlen (what the reference's asserts demand): a job that
  * breaks this gets status -1 and no text, and the call still succeeds.  For MM2AMD_TXT_CIGAR only an operation above 9 is refused; the
  * sequences are not read and may be NULL.
@@ -99,6 +103,8 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
 #define MM2AMD_TXT_CS      1
 #define MM2AMD_TXT_CS_LONG 2
 #define MM2AMD_TXT_MD      3
+#define MM2AMD_TXT_DS      4
+#define MM2AMD_TXT_DS_LONG 5
 typedef struct { const uint8_t *query, *target; int32_t qlen, tlen; const uint32_t *cigar; int32_t n_cigar; } mm2amd_txt_job_t;
 typedef struct { uint64_t off; uint32_t len; int32_t status; } mm2amd_txt_res_t;
 int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap);

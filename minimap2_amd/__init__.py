@@ -119,7 +119,7 @@ F_CIGAR, F_OUT_SAM = 0x004, 0x008  # MM_F_CIGAR, MM_F_OUT_SAM (minimap.h:12-13)
 I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
 EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
 DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
-TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD = 0, 1, 2, 3  # MM2AMD_TXT_*
+TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD, TXT_DS, TXT_DS_LONG = 0, 1, 2, 3, 4, 5  # MM2AMD_TXT_*
 FMT_PATH_DEVICE, FMT_PATH_HOST = 0, 1  # MM2AMD_FMT_PATH_*: who wrote the text of mm_gpu_format_batch_dev
 LL_QREV, LL_QCOMP, LL_TREV = 1, 2, 4  # MM2AMD_LL_*
 LL_PATH_WAVE, LL_PATH_WG, LL_PATH_HOST = 0, 1, 2  # MM2AMD_LL_PATH_*
@@ -355,8 +355,8 @@ def _texts(call, n):
 
 def aln_text_batch(jobs, what):
     """jobs: list of (query_codes, target_codes, cigar) -- nt4 codes 0..4 of the aligned stretches and the CIGAR as len << 4 | op words; the
-    sequences may be None for TXT_CIGAR.  what: TXT_CIGAR, TXT_CS, TXT_CS_LONG or TXT_MD.  Returns each job's text (what the reference's
-    mm_gen_cs / mm_gen_MD return, format.c:364-395; aln_text_kernel), or None for a job whose operations the kernel refuses."""
+    sequences may be None for TXT_CIGAR.  what: TXT_CIGAR, TXT_CS, TXT_CS_LONG, TXT_MD, TXT_DS or TXT_DS_LONG.  Returns each job's text (what the
+    reference's mm_gen_cs / mm_gen_ds / mm_gen_MD return, format.c:364-395; aln_text_kernel), or None for a job whose operations the kernel refuses."""
     n = len(jobs)
     arr = (TxtJob * max(n, 1))()
     keep = []
@@ -551,7 +551,7 @@ _CODE_TO_BASE = bytes(b"ACGTN"[min(c, 4)] for c in range(256))
 class Alignment(object):
     """One hit; field names follow mappy.Alignment (python/mappy.pyx:30-90)."""
     __slots__ = ("ctg", "ctg_len", "r_st", "r_en", "q_st", "q_en", "strand", "mapq", "is_primary", "mlen", "blen", "NM",
-                 "cigar", "score", "dp_score", "rid", "sam_pri", "div", "parent", "id", "cs", "MD")
+                 "cigar", "score", "dp_score", "rid", "sam_pri", "div", "parent", "id", "cs", "MD", "ds")
 
     @property
     def cigar_str(self):
@@ -573,7 +573,7 @@ def _regs_to_alignments(n, regs, names, lens):
         a.strand = -1 if r.rev else 1
         a.mapq, a.is_primary, a.sam_pri = r.mapq, int(r.id == r.parent), r.sam_pri
         a.mlen, a.blen, a.score, a.div, a.parent, a.id = r.mlen, r.blen, r.score, r.div, r.parent, r.id
-        a.cs = a.MD = ""  # filled on request (Aligner.map_batch(cs=, MD=)), as mappy's
+        a.cs = a.MD = a.ds = ""  # filled on request (Aligner.map_batch(cs=, MD=, ds=)), as mappy's
         if r.p:
             ex = r.p.contents
             a.dp_score = ex.dp_score
@@ -847,10 +847,11 @@ class Aligner(object):
             raise errors[0]
         return total[0]
 
-    def run(self, raw=False, cs=False, MD=False):
+    def run(self, raw=False, cs=False, MD=False, ds=False):
         """Maps the staged batch.  Returns one list of alignments per read, or a pair of lists for a read pair.  raw=True returns
         (n_reg, reg, rep_len) ctypes arrays (one entry per read, pairs adjacent) that must be passed to free_raw().
-        cs / MD: fill Alignment.cs (the short form) / Alignment.MD -- one mm2amd_hits_text_batch call per tag over all hits of the batch."""
+        cs / MD / ds: fill Alignment.cs (the short form) / Alignment.MD / Alignment.ds (the short form, mappy's mm_gen_ds with no_iden = 1) --
+        one mm2amd_hits_text_batch call per tag over all hits of the batch."""
         if self._staged is None:
             raise Mm2AmdError("run() without stage()")
         self._active()
@@ -868,12 +869,12 @@ class Aligner(object):
                 per.append(_regs_to_alignments(n_reg[k], regs, self.names, self.lens))
             out.append(per[0] if n_seg[i] == 1 else tuple(per))
         try:
-            if cs or MD:
+            if cs or MD or ds:
                 flat = [a for per in out for seg in (per if isinstance(per, tuple) else (per,)) for a in seg]  # read order, as the records below
                 segs = [k for i in range(n) for k in range(seg_off[i], seg_off[i] + n_seg[i])]
                 ptrs = [reg[k] + j * C.sizeof(Reg1) for k in segs for j in range(n_reg[k])]
                 rds = [items[k][1] for k in segs for j in range(n_reg[k])]
-                for want, what, field in ((cs, TXT_CS, "cs"), (MD, TXT_MD, "MD")):
+                for want, what, field in ((cs, TXT_CS, "cs"), (MD, TXT_MD, "MD"), (ds, TXT_DS, "ds")):
                     if want and ptrs:
                         for a, t in zip(flat, hits_text(self._idx, ptrs, rds, what)):
                             setattr(a, field, t or "")
@@ -902,15 +903,15 @@ class Aligner(object):
         finally:
             _libc_free(out)
 
-    def map_batch(self, reads, cs=False, MD=False):
+    def map_batch(self, reads, cs=False, MD=False, ds=False):
         self.stage(reads)
-        return self.run(cs=cs, MD=MD)
+        return self.run(cs=cs, MD=MD, ds=ds)
 
-    def map(self, seq, seq2=None, name="query", cs=False, MD=False):
+    def map(self, seq, seq2=None, name="query", cs=False, MD=False, ds=False):
         """Single-read (or, with seq2, single-pair) convenience wrapper (mappy.Aligner.map); a batch of one."""
         if seq2 is not None:
-            return self.map_pairs([(name, seq, seq2)], cs=cs, MD=MD)[0]
-        return self.map_batch([(name, seq)], cs=cs, MD=MD)[0]
+            return self.map_pairs([(name, seq, seq2)], cs=cs, MD=MD, ds=ds)[0]
+        return self.map_batch([(name, seq)], cs=cs, MD=MD, ds=ds)[0]
 
     def seq(self, name, start=0, end=0x7fffffff):
         """mappy.Aligner.seq (python/mappy.pyx:239, cmappy.h:122-138): bases [start, end) of the named reference sequence as str, end clipped
@@ -927,13 +928,13 @@ class Aligner(object):
             _check(rc)
         return buf.raw.translate(_CODE_TO_BASE).decode("ascii")
 
-    def map_pairs(self, pairs, text=False, cs=False, MD=False):
+    def map_pairs(self, pairs, text=False, cs=False, MD=False, ds=False):
         """Paired-end reads: pairs = list of (name, seq1, seq2) (use preset "sr").  Returns a list of (alignments of read 1,
-        alignments of read 2), with cs / MD filled on request; with text=True the SAM/PAF records of the batch instead
+        alignments of read 2), with cs / MD / ds filled on request; with text=True the SAM/PAF records of the batch instead
         (mm_gpu_format_batch, mate fields included)."""
         self.stage(pairs)
         if not text:
-            return self.run(cs=cs, MD=MD)
+            return self.run(cs=cs, MD=MD, ds=ds)
         n_reg, reg, rep_len = self.run(raw=True)
         try:
             return self.format_raw(n_reg, reg, rep_len)

@@ -1,16 +1,21 @@
-// Per-base alignment text on the device: the CIGAR string, the cs tag (short and long form) and the MD tag of a batch of alignments -- what the
-// reference writes one hit at a time in write_sam_cigar, write_cs_ds_core (format.c:171-254) and write_MD_core (format.c:302-331).  One
-// wavefront per alignment walks its columns 64 at a time (aln_text_dev.hpp); the output is variable-length, so the kernel runs twice: the first
-// pass checks the operations and counts every job's bytes, the host turns the lengths into 64-bit offsets, the second pass writes.  Both passes
-// run the same per-column emitter.  The ds tag (write_indel_ds) stays with the host formatter.
+// Per-base alignment text on the device: the CIGAR string, the cs tag (short and long form), the ds tag (short and long form) and the MD tag of
+// a batch of alignments -- what the reference writes one hit at a time in write_sam_cigar, write_cs_ds_core with write_indel_ds
+// (format.c:142-254) and write_MD_core (format.c:302-331).  One wavefront per alignment walks its columns 64 at a time (aln_text_dev.hpp); the
+// output is variable-length, so the kernel runs twice: the first pass checks the operations and counts every job's bytes, the host turns the
+// lengths into 64-bit offsets, the second pass writes.  Both passes run the same per-column emitter.  ds is cs with brackets around the bases
+// by which an insertion or a deletion can be shifted: the two extents of every indel are found when its operation is staged, by scans of the
+// aligned query (I) or target (D) that never leave [0, qlen) / [0, tlen) of the job.
 #pragma once
 #include <cstdint>
 
 namespace mm2amd {
 
-constexpr int kTxtCigar = 0, kTxtCs = 1, kTxtCsLong = 2, kTxtMd = 3; // MM2AMD_TXT_* (include/mm2amd.h)
-constexpr int kTxtTileOps = 256;  // CIGAR operations staged in LDS at a time, with their exclusive query / target / column offsets
+constexpr int kTxtCigar = 0, kTxtCs = 1, kTxtCsLong = 2, kTxtMd = 3, kTxtDs = 4, kTxtDsLong = 5; // MM2AMD_TXT_* (include/mm2amd.h)
+constexpr int kTxtTileOps = 256;  // CIGAR operations staged in LDS at a time, with their exclusive query / target / column offsets (ds: and their two shift extents)
+constexpr int kTxtDsLaneScan = 6; // ds: an indel up to this long has its shift extents scanned by one lane (at most this many comparisons each way);
+                                  // a longer one by the whole wave, 64 comparisons a step
 constexpr int kTxtColBytes = 25;  // the most one column emits: ":<10 digits>" of a pending identity run, then "~gt<9 digits>ag" of an intron
+                                  // (a ds indel column stays below it: ":<10 digits>" + "+[a]" is 15 bytes)
 
 // where a job's sequences come from
 constexpr uint32_t kTxtQCodes = 0,     // nt4 codes, forward: base i at qpool[q_pos + i]
@@ -32,7 +37,7 @@ struct TxtRes { uint64_t cols; uint32_t len; int32_t status; }; // columns walke
 
 struct TxtParams {
 	const TxtJob *jobs; int n_jobs;
-	int what;               // kTxtCigar .. kTxtMd
+	int what;               // kTxtCigar .. kTxtDsLong
 	const uint8_t *qpool, *tpool;
 	const uint32_t *S;      // packed reference (kTxtTPacked*)
 	const uint32_t *cigar;

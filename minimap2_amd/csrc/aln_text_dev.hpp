@@ -10,7 +10,10 @@
 //             every column the start of the run it would flush, and so the run's length, without walking it;
 //   bytes     every lane runs the column emitter on a counting sink; wave_inclusive_sum (with a 64-bit carry) turns the counts into
 //             offsets.  The writing pass runs the SAME emitter again on a sink that stores into an LDS stage, placed so that the stage and
-//             the destination agree modulo 4, and the wave copies the stage out in aligned dwords (single bytes at the two ragged ends).
+//             the destination agree modulo 4, and the wave copies the stage out in aligned dwords (single bytes at the two ragged ends);
+//   ds        cs, except that an inserted or deleted stretch carries brackets around the bases by which the gap can be shifted (write_indel_ds).
+//             The two extents of every I / D operation are found when its tile is staged (txt_ds_extents) and kept in two more LDS arrays; a
+//             column of the operation then knows from (its index, len, ll, lr) alone which brackets it carries.
 //
 // The sizing pass validates first (64-bit sums: a CIGAR whose lengths wrap must not pass for one that covers the sequences), so that every
 // sequence index the walk forms lies inside [0, qlen) / [0, tlen).
@@ -69,12 +72,27 @@ struct TxtCol {
 	int kind = TXT_NONE;
 	bool first = false, ident = false; // first column of its operation; query base == target base (by code: N against N is a match)
 	uint32_t pend = 0;                 // identity columns waiting to be flushed before this one
-	uint32_t len = 0;                  // N: the intron's length
+	uint32_t len = 0;                  // N: the intron's length; ds I / D: the operation's length
+	uint32_t j = 0, ll = 0, lr = 0;    // ds I / D: the column's index in its operation; the operation's shift extents (txt_ds_extents)
 	int a = 4, b = 4, c = 4, d = 4;    // M: query, target base; I: a; D: b; N: the first two (a, b) and the last two (c, d) target bases
 };
 
-// The text of one column -- the only place that knows what cs, MD and CIGAR text look like; sizing and writing both go through it.
+// One base of a ds indel with the brackets of write_indel_ds (format.c:142-169) in closed form: ll + lr >= len brackets the whole stretch, otherwise
+// the first ll and the last lr bases.
 template <class Sink>
+__device__ __forceinline__ void txt_emit_ds_base(Sink &o, const TxtCol &k, int base)
+{
+	const bool all = k.ll + k.lr >= k.len;
+	const bool open = k.j == 0u ? (all || k.ll > 0u) : (!all && k.lr > 0u && k.j == k.len - k.lr);
+	const bool close = k.j == k.len - 1u ? (all || k.lr > 0u) : (!all && k.ll > 0u && k.j == k.ll - 1u);
+	if (open) o.ch('[');
+	o.ch(txt_lower(base));
+	if (close) o.ch(']');
+}
+
+// The text of one column -- the only place that knows what cs, ds, MD and CIGAR text look like; sizing and writing both go through it.
+// DS: `what` may be a ds mode (the instances without it carry no code for the brackets).
+template <bool DS, class Sink>
 __device__ __forceinline__ void txt_emit_column(Sink &o, const TxtCol &k, int what)
 {
 	if (k.kind == TXT_NONE) return;
@@ -84,14 +102,14 @@ __device__ __forceinline__ void txt_emit_column(Sink &o, const TxtCol &k, int wh
 		else if (k.kind == TXT_TERM) { if (k.pend > 0) o.num(k.pend); }
 		return;
 	}
-	// write_cs_ds_core with is_ds == 0, format.c:171-254: an identity run ends at a mismatch and at the end of every M / = / X operation
-	const bool lng = what == kTxtCsLong;
+	// write_cs_ds_core, format.c:171-254: an identity run ends at a mismatch and at the end of every M / = / X operation; is_ds changes + and - only
+	const bool lng = what == kTxtCsLong || (DS && what == kTxtDsLong), ds = DS && (what == kTxtDs || what == kTxtDsLong);
 	if (!lng && k.pend > 0 && (!k.ident || k.first)) o.ch(':'), o.num(k.pend);
 	if (k.kind == TXT_M) {
 		if (!k.ident) o.ch('*'), o.ch(txt_lower(k.b)), o.ch(txt_lower(k.a));
 		else if (lng) { if (k.first || k.pend == 0) o.ch('='); o.ch(txt_upper(k.a)); }
-	} else if (k.kind == TXT_I) { if (k.first) o.ch('+'); o.ch(txt_lower(k.a)); }
-	else if (k.kind == TXT_D) { if (k.first) o.ch('-'); o.ch(txt_lower(k.b)); }
+	} else if (k.kind == TXT_I) { if (k.first) o.ch('+'); if (ds) txt_emit_ds_base(o, k, k.a); else o.ch(txt_lower(k.a)); }
+	else if (k.kind == TXT_D) { if (k.first) o.ch('-'); if (ds) txt_emit_ds_base(o, k, k.b); else o.ch(txt_lower(k.b)); }
 	else if (k.kind == TXT_N) o.ch('~'), o.ch(txt_lower(k.a)), o.ch(txt_lower(k.b)), o.num(k.len), o.ch(txt_lower(k.c)), o.ch(txt_lower(k.d));
 }
 template <class Sink>
@@ -196,13 +214,66 @@ struct TxtSeqs { // where the bases of a walk come from (aln_text.hpp: kTxtQ* / 
 	}
 };
 
-// cs (short or long) or MD of a CIGAR that txt_bad_ops has passed; s_word / s_q / s_t / s_col: kTxtTileOps words of LDS each.  Returns the columns walked.
-template <bool WRITE>
+// ds: the shift extents of the nt staged operations (write_cs_ds_core, format.c:209-218 and :228-237).  For an I / D operation of length len that
+// starts at y of its sequence s (the aligned query for I, the aligned target for D; L bases):
+//   lr = the number of i = 1 .. len, from 1 on without a gap, with y - i >= 0 and s[y + len - i] == s[y - i]   (the gap can move left by lr)
+//   ll = the number of z = 0 .. len - 1, from 0 on without a gap, with y + len + z < L and s[y + z] == s[y + len + z]   (... right by ll)
+// The bounds are tested before a base is read, so every index lies in [0, L).  A lane scans the operations up to kTxtDsLaneScan long that it
+// staged, on its own; the wave then takes the longer ones in turn, 64 comparisons a step, the first failure by ballot -- so no lane walks more
+// than kTxtDsLaneScan bases alone, whatever the operation's length (a homopolymer makes every comparison succeed).
+__device__ __forceinline__ void txt_ds_extents(const TxtSeqs &Q, uint32_t nt, const uint32_t *s_word, const uint32_t *s_q, const uint32_t *s_t,
+                                               uint32_t *s_ll, uint32_t *s_lr, int lane)
+{
+	auto base = [&](bool ins, uint32_t i) { return ins ? Q.qbase(i) : Q.tbase(i); };
+	auto left_ok = [&](bool ins, uint32_t y, uint32_t len, uint32_t i) { return y >= i && base(ins, y + len - i) == base(ins, y - i); };                 // i in 1 .. len
+	auto right_ok = [&](bool ins, uint32_t y, uint32_t len, uint32_t L, uint32_t z) { return y + len + z < L && base(ins, y + z) == base(ins, y + len + z); }; // z in 0 .. len - 1
+	for (uint32_t r = 0; r < nt; r += 64u) {
+		const uint32_t i = r + (uint32_t)lane;
+		uint32_t ll = 0, lr = 0;
+		bool wide = false;
+		if (i < nt) {
+			const uint32_t w = s_word[i], op = w & 0xf, len = w >> 4;
+			if (op == 1u || op == 2u) {
+				const bool ins = op == 1u;
+				const uint32_t y = ins ? s_q[i] : s_t[i], L = ins ? Q.qlen : Q.tlen;
+				if (len <= (uint32_t)kTxtDsLaneScan) {
+					while (lr < len && left_ok(ins, y, len, lr + 1u)) ++lr;
+					while (ll < len && right_ok(ins, y, len, L, ll)) ++ll;
+				} else wide = true;
+			}
+		}
+		for (unsigned long long m = __ballot(wide); m; m &= m - 1ull) { // (the same in every lane)
+			const int b = __ffsll((long long)m) - 1;
+			const uint32_t k = r + (uint32_t)b, w = s_word[k], len = w >> 4;
+			const bool ins = (w & 0xf) == 1u;
+			const uint32_t y = ins ? s_q[k] : s_t[k], L = ins ? Q.qlen : Q.tlen;
+			uint32_t zl = len, zr = len; // a lane beyond len fails, so the last step of a scan that runs to the end still ends it at len
+			for (uint32_t z0 = 0; z0 < len; z0 += 64u) {
+				const uint32_t z = z0 + (uint32_t)lane;
+				const unsigned long long f = __ballot(!(z < len && left_ok(ins, y, len, z + 1u)));
+				if (f) { zr = z0 + (uint32_t)(__ffsll((long long)f) - 1); break; }
+			}
+			for (uint32_t z0 = 0; z0 < len; z0 += 64u) {
+				const uint32_t z = z0 + (uint32_t)lane;
+				const unsigned long long f = __ballot(!(z < len && right_ok(ins, y, len, L, z)));
+				if (f) { zl = z0 + (uint32_t)(__ffsll((long long)f) - 1); break; }
+			}
+			if (lane == b) ll = zl, lr = zr;
+		}
+		if (i < nt) s_ll[i] = ll, s_lr[i] = lr;
+	}
+}
+
+// cs or ds (short or long) or MD of a CIGAR that txt_bad_ops has passed; s_word / s_q / s_t / s_col: kTxtTileOps words of LDS each.  DS: the walk
+// can write ds, and s_ll / s_lr are two more such arrays; without it they are not touched (and `what` is not a ds mode).  Returns the columns walked.
+template <bool WRITE, bool DS = false>
 __device__ __forceinline__ uint32_t txt_walk_columns(TxtOut<WRITE> &O, const TxtSeqs &Q, int what, const uint32_t *cg, uint32_t n,
-                                                     uint32_t *s_word, uint32_t *s_q, uint32_t *s_t, uint32_t *s_col)
+                                                     uint32_t *s_word, uint32_t *s_q, uint32_t *s_t, uint32_t *s_col,
+                                                     uint32_t *s_ll = nullptr, uint32_t *s_lr = nullptr)
 {
 	const int lane = O.lane;
 	const bool md = what == kTxtMd;
+	const bool ds = DS && (what == kTxtDs || what == kTxtDsLong);
 	uint32_t cq = 0, ct = 0, ccol = 0; // what the operations staged so far consume: query, target, columns
 	uint32_t run_from = 0;             // the column the pending identity run starts at (max over the columns walked so far)
 	// one step: the lane's column c (or none) -> its text
@@ -222,6 +293,7 @@ __device__ __forceinline__ uint32_t txt_walk_columns(TxtOut<WRITE> &O, const Txt
 				k.kind = TXT_N, k.len = w >> 4;
 				k.a = Q.tbase(t0), k.b = Q.tbase(t0 + 1u), k.c = Q.tbase(t0 + k.len - 2u), k.d = Q.tbase(t0 + k.len - 1u);
 			} else k.kind = TXT_M, k.a = Q.qbase(s_q[lo] + j), k.b = Q.tbase(s_t[lo] + j), k.ident = k.a == k.b;
+			if (DS && ds && (op == 1u || op == 2u)) k.len = w >> 4, k.j = j, k.ll = s_ll[lo], k.lr = s_lr[lo];
 			if (md) next_run = k.ident ? 0u : c + 1u;          // a mismatch or a deleted base: the count starts again behind it
 			else next_run = !k.ident ? c + 1u : k.first ? c : 0u; // cs: ... and an operation's first column starts a run of its own
 		}
@@ -233,10 +305,10 @@ __device__ __forceinline__ uint32_t txt_walk_columns(TxtOut<WRITE> &O, const Txt
 		run_from = last > run_from ? last : run_from;
 		if (active) k.pend = c - before;
 		TxtCount cnt;
-		txt_emit_column(cnt, k, what);
+		txt_emit_column<DS>(cnt, k, what);
 		uint32_t a, excl;
 		const uint32_t tot = O.place(cnt.n, a, excl);
-		if (WRITE && cnt.n) { TxtStore s; s.p = (char *)O.stage + a + excl; txt_emit_column(s, k, what); }
+		if (WRITE && cnt.n) { TxtStore s; s.p = (char *)O.stage + a + excl; txt_emit_column<DS>(s, k, what); }
 		O.flush(a, tot);
 	};
 
@@ -260,6 +332,10 @@ __device__ __forceinline__ uint32_t txt_walk_columns(TxtOut<WRITE> &O, const Txt
 			cq += (uint32_t)__shfl((int)iq, 63, 64), ct += (uint32_t)__shfl((int)it, 63, 64), ccol += (uint32_t)__shfl((int)ic, 63, 64);
 		}
 		TXT_SYNC();
+		if (DS && ds) {
+			txt_ds_extents(Q, nt, s_word, s_q, s_t, s_ll, s_lr, lane);
+			TXT_SYNC();
+		}
 		for (unsigned long long c0 = col0; c0 < ccol; c0 += 64ull) { // (64 bits: columns may reach 2^32 - 2)
 			const unsigned long long c = c0 + (unsigned long long)lane;
 			step(c < ccol, (uint32_t)c, nt, false);
@@ -271,10 +347,12 @@ __device__ __forceinline__ uint32_t txt_walk_columns(TxtOut<WRITE> &O, const Txt
 
 } // namespace
 
-template <bool WRITE>
+// DS: the instance for the two ds modes, with the two arrays of shift extents; the other modes run the instance without them.
+template <bool WRITE, bool DS>
 __global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
 {
 	__shared__ uint32_t s_word[kTxtTileOps], s_q[kTxtTileOps], s_t[kTxtTileOps], s_col[kTxtTileOps];
+	__shared__ uint32_t s_ll[DS ? kTxtTileOps : 1], s_lr[DS ? kTxtTileOps : 1];
 	__shared__ uint32_t s_stage[(64 * kTxtColBytes + 4 + 3) / 4 + 1];
 	const int lane = (int)threadIdx.x;
 	const int id = (int)blockIdx.x;
@@ -298,7 +376,7 @@ __global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
 	else {
 		TxtSeqs Q;
 		Q.qpool = P.qpool, Q.tpool = P.tpool, Q.S = P.S, Q.q_pos = J.q_pos, Q.t_pos = J.t_pos, Q.qlen = (uint32_t)J.qlen, Q.tlen = (uint32_t)J.tlen, Q.qsrc = J.qsrc, Q.tsrc = J.tsrc;
-		cols = txt_walk_columns(O, Q, what, cg, n, s_word, s_q, s_t, s_col);
+		cols = txt_walk_columns<WRITE, DS>(O, Q, what, cg, n, s_word, s_q, s_t, s_col, s_ll, s_lr);
 	}
 	if (!WRITE && lane == 0) { TxtRes r; r.cols = cols, r.len = (uint32_t)O.nbytes, r.status = O.nbytes > 0xffffffffull ? -1 : 0; if (r.status) r.len = 0; P.res[id] = r; }
 }
@@ -306,8 +384,11 @@ __global__ void __launch_bounds__(64) aln_text_kernel(TxtParams P)
 void aln_text_launch(const TxtParams &P, bool write, void *stream)
 {
 	if (P.n_jobs <= 0) return;
-	if (write) hipLaunchKernelGGL(aln_text_kernel<true>, dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
-	else hipLaunchKernelGGL(aln_text_kernel<false>, dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
+	const bool ds = P.what == kTxtDs || P.what == kTxtDsLong;
+	if (write && ds) hipLaunchKernelGGL((aln_text_kernel<true, true>), dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
+	else if (write) hipLaunchKernelGGL((aln_text_kernel<true, false>), dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
+	else if (ds) hipLaunchKernelGGL((aln_text_kernel<false, true>), dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
+	else hipLaunchKernelGGL((aln_text_kernel<false, false>), dim3(P.n_jobs), dim3(64), 0, (hipStream_t)stream, P);
 	HIP_CHECK(hipGetLastError());
 }
 

@@ -220,7 +220,7 @@ int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *co
                            int what, int is_qstrand, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
 {
 	if (!idx) return capi_fail(MM2AMD_EINVAL, "[mm2amd] null index");
-	if (n_hits < 0 || (n_hits > 0 && (!hit || !qseq || !qlen || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_MD) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: bad arguments");
+	if (n_hits < 0 || (n_hits > 0 && (!hit || !qseq || !qlen || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_DS_LONG) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: bad arguments");
 	const IndexHandle *h = (const IndexHandle *)idx;
 	const FlatIndex &fi = h->fi;
 	if ((fi.flag & ref::I_NO_SEQ) || !fi.S || !h->T.S.p) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: the index holds no sequence");

@@ -305,7 +305,7 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
 
 int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
 {
-	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_MD) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad arguments");
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_DS_LONG) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad arguments");
 	if (n_jobs == 0) return 0;
 	return guarded([&]() -> int {
 		const bool seqs = what != MM2AMD_TXT_CIGAR;

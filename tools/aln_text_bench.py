@@ -4,11 +4,12 @@
     python tools/aln_text_bench.py [--reads 3000] [--ref-mb 5] [--threads 8] [--out profiles/aln_text_bench.json]
 
 Maps synthetic ONT reads (tests/synth.py), then
-  * times mm2amd_hits_text_batch for cs and MD over all hits of the batch: wall time of the sizing call and of the writing call (uploads,
-    both passes of aln_text_kernel, the copy back), and the kernel's own milliseconds from mm2amd_profile_get;
-  * times the host writers on the same records: mm_gpu_format_batch (PAF) with and without MM_F_OUT_CS / MM_F_OUT_MD -- the difference is
-    what put_cs / put_md cost on the host pool -- and, where the compiled reference is present (oracle/_ref), its mm_gen_cs / mm_gen_MD
-    called hit by hit on one thread.
+  * times mm2amd_hits_text_batch for cs, MD and ds over all hits of the batch: wall time of the sizing call and of the writing call (uploads,
+    both passes of aln_text_kernel, the copy back), and the kernel's own milliseconds from mm2amd_profile_get; the ds row also as a ratio
+    to the cs row of the same run (ds is cs plus the shift scans of every indel);
+  * times the host writers on the same records: mm_gpu_format_batch (PAF) with and without MM_F_OUT_CS / MM_F_OUT_MD / MM_F_OUT_DS -- the
+    difference is what put_cs (with is_ds for ds) / put_md cost on the host pool -- and, where the compiled reference is present
+    (oracle/_ref), its mm_gen_cs / mm_gen_MD / mm_gen_ds called hit by hit on one thread.
 One JSON object, printed and written to --out."""
 import argparse
 import ctypes as C
@@ -22,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-F_OUT_CS, F_OUT_MD = 0x040, 0x1000000  # MM_F_OUT_CS, MM_F_OUT_MD (minimap.h:16, :34)
+F_OUT_CS, F_OUT_MD, F_OUT_DS = 0x040, 0x1000000, 0x2000000000  # MM_F_OUT_CS, MM_F_OUT_MD, MM_F_OUT_DS (minimap.h:16, :34, :47)
 
 
 def main(argv=None):
@@ -64,7 +65,7 @@ def main(argv=None):
         harr, qarr, qlen = (C.c_void_p * nh)(*ptrs), (C.c_char_p * nh)(*hit_reads), (C.c_int32 * nh)(*[len(r) for r in hit_reads])
         out = (mm.TxtRes * nh)()
         # ---- the device ----
-        for tag, what in (("cs", mm.TXT_CS), ("MD", mm.TXT_MD)):
+        for tag, what in (("cs", mm.TXT_CS), ("MD", mm.TXT_MD), ("ds", mm.TXT_DS)):
             best = None
             for _ in range(a.repeat + 1):  # (the first pass allocates)
                 mm.profile_enable(True)
@@ -86,6 +87,8 @@ def main(argv=None):
                     best = cur
             best["kernel_write_gb_per_s"] = best["text_bytes"] / max(best["kernel_write_ms"], 1e-9) / 1e6
             res["device_" + tag] = best
+        res["device_ds"]["over_cs"] = {k: res["device_ds"][k] / max(res["device_cs"][k], 1e-9)
+                                       for k in ("sizing_call_ms", "writing_call_ms", "kernel_size_ms_per_launch", "kernel_write_ms", "text_bytes")}
 
         # ---- the host writers on the same records ----
         def format_ms(extra):
@@ -104,8 +107,10 @@ def main(argv=None):
         base, base_bytes = format_ms(0)
         cs_ms, cs_bytes = format_ms(F_OUT_CS)
         md_ms, md_bytes = format_ms(F_OUT_MD)
-        res["host_format_batch"] = {"paf_ms": base, "paf_cs_ms": cs_ms, "paf_md_ms": md_ms, "cs_ms": cs_ms - base, "md_ms": md_ms - base,
-                                    "cs_bytes": cs_bytes - base_bytes, "md_bytes": md_bytes - base_bytes, "threads": a.threads}
+        ds_ms, ds_bytes = format_ms(F_OUT_DS)
+        res["host_format_batch"] = {"paf_ms": base, "paf_cs_ms": cs_ms, "paf_md_ms": md_ms, "paf_ds_ms": ds_ms, "cs_ms": cs_ms - base, "md_ms": md_ms - base,
+                                    "ds_ms": ds_ms - base, "cs_bytes": cs_bytes - base_bytes, "md_bytes": md_bytes - base_bytes, "ds_bytes": ds_bytes - base_bytes,
+                                    "threads": a.threads}
         res["reference_loop"] = None
         if os.path.exists(reflib.REF_SO):  # the compiled reference's writers, hit by hit on one thread (ctypes call overhead included)
             R = C.CDLL(reflib.REF_SO)
@@ -113,6 +118,7 @@ def main(argv=None):
             R.mm_idx_str.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
             R.mm_gen_cs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
             R.mm_gen_MD.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_char_p]
+            R.mm_gen_ds.argtypes = R.mm_gen_cs.argtypes
             R.mm_idx_destroy.argtypes = [C.c_void_p]
             mi = R.mm_idx_str(al.idx_opt.w, al.idx_opt.k, 0, 14, 2, (C.c_char_p * 2)(*refs), (C.c_char_p * 2)(*[x.encode() for x in names]))
             buf, cap = C.c_void_p(), C.c_int(0)
@@ -121,10 +127,14 @@ def main(argv=None):
             t1 = time.perf_counter()
             nb_md = sum(R.mm_gen_MD(None, C.byref(buf), C.byref(cap), mi, p, r) for p, r in zip(ptrs, hit_reads))
             t2 = time.perf_counter()
+            nb_ds = sum(R.mm_gen_ds(None, C.byref(buf), C.byref(cap), mi, p, r, 1) for p, r in zip(ptrs, hit_reads))
+            t3 = time.perf_counter()
             mm._libc_free(buf)
             R.mm_idx_destroy(mi)
-            res["reference_loop"] = {"cs_ms": (t1 - t0) * 1e3, "md_ms": (t2 - t1) * 1e3, "cs_bytes": nb_cs, "md_bytes": nb_md, "threads": 1}
-            assert nb_cs == res["device_cs"]["text_bytes"] and nb_md == res["device_MD"]["text_bytes"], "the device's text and the reference's differ in length"
+            res["reference_loop"] = {"cs_ms": (t1 - t0) * 1e3, "md_ms": (t2 - t1) * 1e3, "ds_ms": (t3 - t2) * 1e3, "cs_bytes": nb_cs, "md_bytes": nb_md,
+                                     "ds_bytes": nb_ds, "threads": 1}
+            assert nb_cs == res["device_cs"]["text_bytes"] and nb_md == res["device_MD"]["text_bytes"] and nb_ds == res["device_ds"]["text_bytes"], \
+                "the device's text and the reference's differ in length"
         al.free_raw(n_reg, reg)
     finally:
         L.mm_gpu_destroy()
