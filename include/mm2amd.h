@@ -82,6 +82,15 @@ typedef struct { int32_t n_cigar, blen, mlen, n_ambi, dp_max, qshift, tshift, is
 int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
                               mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap);
 
+/* mm_update_extra with is_eqx = 1: the same jobs, the same result fields, and on top mm_update_cigar_eqx (align.c:183-252) -- every match
+ * operation cut into its maximal stretches of equal (=, operation 7) and unequal (X, 8) columns, N against N being equal; a CIGAR none of whose
+ * matches splits is relabelled M -> = as it stands, as the reference does in place (cigar_eqx_kernel after region_finish_kernel, one wavefront
+ * per region).  n_cigar and the operations are the =/X ones; they can outnumber the sum of the piece lengths, so the pool is sized by a call of
+ * its own: cigar_pool == NULL fills every res[i] (n_cigar and cigar_off included) and returns 0; a pool smaller than the sum of the n_cigar
+ * returns MM2AMD_ENOMEM with the results filled and nothing written.  MM2AMD_FIN_MAX_OPS bounds the operations coming in, as above. */
+int mm2amd_update_extra_eqx_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
+                                  mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap);
+
 /* Alignment text on the device (aln_text_kernel, one wavefront per alignment): the per-base strings the reference writes hit by hit.
  *   MM2AMD_TXT_CIGAR    "<len><op>" per operation, op letter from "MIDNSHP=XB" (write_sam_cigar, format.c)
  *   MM2AMD_TXT_CS       the short cs string, identity runs as ":n" (write_cs_ds_core with no_iden = 1 and is_ds = 0, format.c:171-254)

@@ -116,6 +116,7 @@ class KernelStat(C.Structure):  # mm2amd_kernel_stat_t
 assert C.sizeof(MapOpt) == 264 and C.sizeof(Reg1) == 80 and C.sizeof(Extra) == 28 and C.sizeof(Bseq1) == 40 and C.sizeof(IdxOpt) == 24
 
 F_CIGAR, F_OUT_SAM = 0x004, 0x008  # MM_F_CIGAR, MM_F_OUT_SAM (minimap.h:12-13)
+F_EQX = 0x4000000  # MM_F_EQX (minimap.h:36): --eqx, match operations written as = and X
 I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
 EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
 DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
@@ -159,6 +160,8 @@ def _bind(L):
                                              C.POINTER(KswRes), C.POINTER(C.c_uint32), C.c_size_t]
         L.mm2amd_update_extra_batch.restype = C.c_int
         L.mm2amd_update_extra_batch.argtypes = [C.c_int, C.POINTER(FinJob), C.c_char_p, C.c_int8, C.c_int8, C.c_int, C.POINTER(FinRes), C.POINTER(C.c_uint32), C.c_size_t]
+        L.mm2amd_update_extra_eqx_batch.restype = C.c_int
+        L.mm2amd_update_extra_eqx_batch.argtypes = L.mm2amd_update_extra_batch.argtypes
         L.mm2amd_aln_text_batch.argtypes = [C.c_int, C.POINTER(TxtJob), C.c_int, C.POINTER(TxtRes), vp, C.c_size_t]
         L.mm2amd_hits_text_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(TxtRes), vp,
                                              C.c_size_t]
@@ -316,10 +319,8 @@ def read_fastx(fn):
     return names, seqs
 
 
-def update_extra_batch(jobs, mat, q, e, log_gap):
-    """jobs: list of (query_codes, target_codes, [piece, ...]) -- nt4 codes 0..4 of the aligned stretches and the windows' CIGARs (sequences of
-    len << 4 | op) in alignment order.  Returns a list of (cigar_tuple, blen, mlen, n_ambi, dp_max, qshift, tshift, is_spliced) -- what the
-    reference's mm_update_extra (align.c:254-303) leaves in the hit record -- or None for a region whose operations do not cover its stretches."""
+def fin_jobs(jobs):
+    """jobs of update_extra_batch as the C ABI's array: (FinJob array, the objects it points into -- keep them alive --, the sum of the piece lengths)"""
     n = len(jobs)
     arr = (FinJob * max(n, 1))()
     keep, tot = [], 0
@@ -332,9 +333,23 @@ def update_extra_batch(jobs, mat, q, e, log_gap):
         arr[i].query, arr[i].target = C.cast(C.c_char_p(qb), C.c_void_p), C.cast(C.c_char_p(tb), C.c_void_p)
         arr[i].qlen, arr[i].tlen, arr[i].n_pieces, arr[i].piece, arr[i].piece_len = len(qb), len(tb), len(pieces), pp, pl
         tot += sum(len(p_) for p_ in pieces)
+    return arr, keep, tot
+
+
+def update_extra_batch(jobs, mat, q, e, log_gap, eqx=False):
+    """jobs: list of (query_codes, target_codes, [piece, ...]) -- nt4 codes 0..4 of the aligned stretches and the windows' CIGARs (sequences of
+    len << 4 | op) in alignment order.  Returns a list of (cigar_tuple, blen, mlen, n_ambi, dp_max, qshift, tshift, is_spliced) -- what the
+    reference's mm_update_extra (align.c:254-303) leaves in the hit record -- or None for a region whose operations do not cover its stretches.
+    eqx: with is_eqx set -- the matches cut into = and X (mm_update_cigar_eqx, align.c:183-252; mm2amd_update_extra_eqx_batch)."""
+    n = len(jobs)
+    arr, keep, tot = fin_jobs(jobs)
     res = (FinRes * max(n, 1))()
+    if eqx:  # the sizing call, then the real one
+        _check(lib().mm2amd_update_extra_eqx_batch(n, arr, bytes(mat), q, e, 1 if log_gap else 0, res, None, 0))
+        tot = sum(max(r.n_cigar, 0) for r in res[:n])
     pool = (C.c_uint32 * max(tot, 1))()
-    _check(lib().mm2amd_update_extra_batch(n, arr, bytes(mat), q, e, 1 if log_gap else 0, res, pool, max(tot, 1)))
+    call = lib().mm2amd_update_extra_eqx_batch if eqx else lib().mm2amd_update_extra_batch
+    _check(call(n, arr, bytes(mat), q, e, 1 if log_gap else 0, res, pool, max(tot, 1)))
     out = []
     for i in range(n):
         r = res[i]
@@ -639,14 +654,14 @@ class Aligner(object):
     fn_idx_in: instead of seq, a file -- a minimap2 index (.mmi, read by mm2amd_idx_load; part: which part of a multi-part file, required when
     there is more than one; the file's k, w and flags replace the preset's) or FASTA / FASTQ, plain or gzip.  fn_idx_out: write the index there
     as a .mmi (mm2amd_idx_dump) once it is built.  extra_flags: MM_F_* bits ORed into map_opt.flag (mappy's parameter of the same name).
-    sdust_thres: minimap2's -T (minimizers lying mostly in SDUST-masked stretches of a read are dropped; 0 = off).
+    sdust_thres: minimap2's -T (minimizers lying mostly in SDUST-masked stretches of a read are dropped; 0 = off).  eqx: minimap2's --eqx (MM_F_EQX).
     n_gpus / device_ids: map every batch on several GPUs of this process (mm_gpu_init_index_multi: index replicated, reads sharded
     by bases; an ordinal may repeat).  Only one Aligner can be the active mapper of the process at a time (the drop-in boundary is
     a process-wide context, like the reference's pipeline): creating a second one makes the first inactive -- its map calls raise,
     and closing or collecting it leaves the new context alone."""
 
     def __init__(self, seq=None, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None,
-                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0):
+                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0, eqx=False):
         L = lib()
         self._generation, self._idx, self._staged = 0, None, None  # close() must work on a half-built object
         self.last_format_path = None  # FMT_PATH_* of the last format_raw(device=True)
@@ -665,6 +680,8 @@ class Aligner(object):
         if sam:
             self.map_opt.flag |= F_OUT_SAM | F_CIGAR
         self.map_opt.flag |= extra_flags  # MM_F_* bits beyond the preset's (mappy.Aligner's extra_flags)
+        if eqx:
+            self.map_opt.flag |= F_EQX  # minimap2's --eqx
         if sdust_thres:
             self.map_opt.sdust_thres = sdust_thres
         from_index = fn_idx_in is not None and idx_is_idx(fn_idx_in)

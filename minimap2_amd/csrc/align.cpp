@@ -1035,7 +1035,7 @@ void Aligner::describe_finish(const ReadAlign &ra, int ti, FinRegion &fr) const
 	fr.q_len = t.qe1 - t.qs1, fr.t_len = t.re1 - t.rs1;
 }
 
-bool Aligner::complete_finished(ReadAlign &ra, const FinResult *results, const FinRegion *regions, const uint32_t *cigars)
+bool Aligner::complete_finished(ReadAlign &ra, const FinResult *results, const FinRegion *regions, const uint32_t *cigars, const EqxOut &eqx)
 {
 	hostprof::Scope hp(hostprof::COMPLETE_FINISHED);
 	const std::vector<int> queue = ra.finish_queue; // (after_finalize may queue nothing, but it does touch ra.tasks)
@@ -1047,12 +1047,14 @@ bool Aligner::complete_finished(ReadAlign &ra, const FinResult *results, const F
 		{
 			RegionTask &t = ra.tasks[ti];
 			Reg &r = t.r;
-			const uint32_t cap = t.sim_cap; // >= the stitched length + header, and mm_fix_cigar only shortens
-			if ((uint32_t)f.n_cigar + kExtraWords > cap) throw std::runtime_error("[mm2amd] region_finish: CIGAR longer than its windows' CIGARs");
+			if ((uint32_t)f.n_cigar + kExtraWords > t.sim_cap) throw std::runtime_error("[mm2amd] region_finish: CIGAR longer than its windows' CIGARs"); // (sim_cap >= the stitched length + header, and mm_fix_cigar only shortens)
+			// MM_F_EQX: the operations are cigar_eqx_kernel's, the container what mm_update_cigar_eqx leaves (align.c:209-221; cigar_to_eqx above)
+			const uint32_t n_cigar = eqx.n_ops ? eqx.n_ops[k] : (uint32_t)f.n_cigar;
+			const uint32_t cap = eqx.n_ops ? eqx_capacity(t.sim_cap, (uint32_t)f.n_cigar, n_cigar, (uint32_t)sizeof(Extra)) : t.sim_cap;
 			r.p = (Extra *)calloc(cap, 4);
 			r.p->capacity = cap;
-			r.p->n_cigar = (uint32_t)f.n_cigar;
-			memcpy(r.p->cigar, cigars + regions[k].out_off, (size_t)f.n_cigar * 4);
+			r.p->n_cigar = n_cigar;
+			memcpy(r.p->cigar, eqx.n_ops ? eqx.cigars + eqx.off[k] : cigars + regions[k].out_off, (size_t)n_cigar * 4);
 			r.p->dp_score = t.dp_acc, r.p->dp_max = r.p->dp_max0 = f.dp_max, r.p->n_ambi = (uint32_t)f.n_ambi;
 			r.blen = f.blen, r.mlen = f.mlen, r.is_spliced = f.is_spliced;
 			if (f.qshift) { if (r.rev) r.qe -= f.qshift; else r.qs += f.qshift; } // mm_fix_cigar's dropped leading gap (align.c:171-180)
@@ -1189,7 +1191,7 @@ bool Aligner::consume_region(ReadAlign &ra, int ti, const KswRes *res, const uin
 			}
 		}
 		hp.stop();
-		if (!t.host_mode && device_finish_ && !qstrand_ && !(opt_.flag & F_EQX)) { // every window came back in this round: the device stitches and finishes it
+		if (!t.host_mode && device_finish_ && !qstrand_ && (!(opt_.flag & F_EQX) || (device_eqx_ && !(opt_.flag & F_SPLICE)))) { // every window came back in this round: the device stitches and finishes it (=/X CIGARs of spliced reads stay here)
 			size_t n_ops = 0;
 			for (const FinPiece &pc : t.pieces) n_ops += pc.n;
 			if (n_ops > 0 && n_ops <= (size_t)kFinMaxOps) {

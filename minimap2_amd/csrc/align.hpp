@@ -11,6 +11,7 @@
 #include "flat_index.hpp"
 #include "ksw_dev.hpp"
 #include "region_finish.hpp"
+#include "cigar_eqx.hpp"
 
 namespace mm2amd {
 
@@ -99,9 +100,9 @@ public:
 	// With device_finish(true), consume() leaves the regions it could finish in ra.finish_queue; the caller sends them through
 	// Backend::finish_regions (describe_finish fills one record per queued task) and hands the results back: complete_finished() does what
 	// follows a region's completion (strand choice, split-off tails, inversion rescue) and returns whether the read still has unfinished work.
-	void device_finish(bool on) { device_finish_ = on; }
+	void device_finish(bool on, bool eqx = false) { device_finish_ = on, device_eqx_ = eqx; } // eqx: the device also cuts the matches into = and X (cigar_eqx.hpp); without it --eqx regions are finished here
 	void describe_finish(const ReadAlign &ra, int ti, FinRegion &fr) const; // everything but piece0 / out_off
-	bool complete_finished(ReadAlign &ra, const FinResult *results, const FinRegion *regions, const uint32_t *cigars);
+	bool complete_finished(ReadAlign &ra, const FinResult *results, const FinRegion *regions, const uint32_t *cigars, const EqxOut &eqx = EqxOut());
 	// Collect the regions in output order and run the post-alignment steps of mm_align_skeleton (:1110-1118).
 	void finish_read(ReadAlign &ra, RegVec &out);
 	void finish_regs(int qlen, RegVec &out) const; // ... its second half: `out` holds the read's aligned regions in output order
@@ -120,7 +121,7 @@ private:
 	bool after_finalize(ReadAlign &ra, int ti);
 	void take_piece(RegionTask &t, const Window &w, const KswRes &ez, const uint32_t *cg, const uint32_t *cigar_pool);
 	void materialize(RegionTask &t, const uint32_t *cigar_pool);
-	bool device_finish_ = false;
+	bool device_finish_ = false, device_eqx_ = false;
 	void try_inversion(ReadAlign &ra, int prev_ti, int ti, int pos_in_order);
 
 	const ref::MapOpt &opt_;

@@ -8,6 +8,7 @@
 #include "flat_index.hpp"
 #include "ksw_dev.hpp"
 #include "region_finish.hpp"
+#include "cigar_eqx.hpp"
 #include "region_dev.hpp"
 #include "rec_text.hpp"
 
@@ -88,7 +89,8 @@ public:
 	virtual void ksw(const std::vector<KswJob> &jobs, const KswScoring &sc, int lane, int n_threads, std::vector<KswRes> &res, const uint32_t **cigar) = 0;
 	// The regions' last step on the device (region_finish.hpp): stitches the windows' CIGARs of this lane's LAST ksw() call (pieces address its
 	// pool), left-aligns and counts as mm_update_extra does.  results[i] belongs to regions[i]; its CIGAR is at *cigars + regions[i].out_off
-	// (backend-owned, valid until the lane's next call).  out_words = room needed in the output pool.
+	// (backend-owned, valid until the lane's next call).  out_words = room needed in the output pool.  eqx non-null: the =/X pass runs on top and
+	// *eqx says where its CIGARs are (results[i].n_cigar stays the count before it: the two tell whether the CIGAR was relabelled in place).
 	// The whole base-level alignment of a sub-batch's reads (round 6: and of short-read pairs, segment by segment) on the device (region_dev.hpp): the chains of this lane's LAST
 	// seed_chain() call become hit records, DP windows, DP results and finished regions without crossing PCIe; what comes back are the finished
 	// hit records (host views, valid until the lane's next align_regions()).  in[i].skip: the host keeps read i.  A read whose RgnReadOut::flags
@@ -99,8 +101,12 @@ public:
 		const FinRegion *fin = nullptr; const FinResult *fin_res = nullptr; const uint32_t *cigars = nullptr;
 		uint32_t n_regs = 0; size_t n_jobs = 0; double dp_cells = 0;
 		int rout_stride = 1; // reads[] holds one entry per read, or (2: the sub-batch has two-segment fragments) two, one per segment
+		EqxOut eqx;          // RgnOpts::flag has MM_F_EQX: the regions' =/X CIGARs (cigar_eqx.hpp), indexed like fin_res
 	};
 	virtual bool aligns_regions() const { return false; }
+	// MM_F_EQX: finish_regions() and align_regions() cut the finished CIGARs' matches into = and X (cigar_eqx.hpp).  false: --eqx reads take the
+	// host's plan / consume rounds and the host's mm_update_cigar_eqx
+	virtual bool eqx_regions() const { return false; }
 	virtual void align_regions(int /*lane*/, const RgnOpts & /*O*/, const KswScoring & /*sc*/, bool /*log_gap*/, const std::vector<ReadChains> & /*chains*/, const std::vector<RegionReadIn> & /*in*/,
 	                           int /*n_threads*/, RegionBatchOut & /*out*/) {}
 	// the chained anchors and minimizer positions of the listed reads of this lane's last seed_chain(.., lazy_chains) come to the host
@@ -119,7 +125,7 @@ public:
 	virtual const char *rec_text_write(uint64_t /*total*/) { return nullptr; }
 	virtual bool finishes_regions() const { return false; }
 	virtual void finish_regions(int /*lane*/, const std::vector<FinRegion> & /*regions*/, const std::vector<FinPiece> & /*pieces*/, size_t /*out_words*/, const int8_t * /*mat25*/,
-	                            int /*q*/, int /*e*/, bool /*log_gap*/, std::vector<FinResult> & /*results*/, const uint32_t ** /*cigars*/) {}
+	                            int /*q*/, int /*e*/, bool /*log_gap*/, std::vector<FinResult> & /*results*/, const uint32_t ** /*cigars*/, EqxOut * /*eqx*/ = nullptr) {}
 };
 
 } // namespace mm2amd

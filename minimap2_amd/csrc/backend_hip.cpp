@@ -63,6 +63,8 @@ struct Lane {
 	PinBuf<unsigned long long> h_lj_cursor;
 	DevBuf<FinRegion> d_fin_regions; DevBuf<FinPiece> d_fin_pieces; DevBuf<uint32_t> d_fin_out; DevBuf<FinResult> d_fin_res; // region_finish.hip
 	PinBuf<FinRegion> h_fin_regions; PinBuf<FinPiece> h_fin_pieces; PinBuf<uint32_t> h_fin_out; PinBuf<FinResult> h_fin_res;
+	struct EqxBufs { DevBuf<uint32_t> d_n, d_out; DevBuf<uint64_t> d_off; PinBuf<uint32_t> h_n, h_out; PinBuf<uint64_t> h_off; }; // cigar_eqx_dev.hpp: the regions' =/X lengths, their places, the pool
+	EqxBufs eqx_fin, eqx_rg; // of finish_regions / of align_regions: the views align_regions hands out live on while the hand-backs' rounds call finish_regions
 	// align_regions (region_dev.hpp): the lane's last seed_chain() in device terms, the hit / window / piece arrays, the results' host copies
 	long rg_lo = 0; size_t rg_n = 0; uint64_t rg_n_v = 0, rg_n_v2 = 0, rg_n_u = 0, rg_n_u2 = 0;
 	std::vector<int8_t> rg_src; std::vector<uint64_t> rg_aoff, rg_uoff; std::vector<int32_t> rg_nu, rg_nv;
@@ -891,6 +893,7 @@ public:
 			kp.begin(st);
 			region_finish_launch(P, st);
 			kp.end(st, "region_finish_kernel", (double)out_words * 8.0 + (double)cur[RGN_CUR_N_FIN] * (sizeof(FinRegion) + sizeof(FinResult)), (double)cur[RGN_CUR_N_FIN]);
+			if (O.flag & ref::F_EQX) out.eqx = eqx_pass(ln, ln.eqx_rg, kp, ln.d_rg_fin.p, n_regs, ln.d_rg_finres.p, ln.d_rg_out.p, out_words, R.d_qpool.p);
 		}
 		RgnReadOut *h_rout = ln.h_rg_rout.ensure(n * (size_t)stride);
 		ref::Reg1 *h_regs = ln.h_rg_regs.ensure(n_regs + 1);
@@ -910,6 +913,7 @@ public:
 		if (out_words) HIP_CHECK(hipMemcpyAsync(h_out, ln.d_rg_out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
 		stream_wait(st);
 		Trace::get().add(lane_id, "gpu:consume+finish, d2h:hits", tt, Trace::now());
+		eqx_sequence_bytes(kp, out.eqx, h_fin, h_finres, n_regs);
 		kp.collect();
 		out.reads = h_rout, out.regs = h_regs, out.aux = h_aux, out.plan = h_plan, out.fin = h_fin, out.fin_res = h_finres, out.cigars = h_out;
 		out.n_regs = n_regs, out.n_jobs = n_jobs, out.rout_stride = stride;
@@ -920,6 +924,55 @@ public:
 	// 1 % slower with it (1.486 / 1.487 against 1.504 / 1.499 Gbases/s, A/B on one box: profiles/README.md); a rank of a multi-GPU job that shares
 	// the node's CPU quota with seven others (two threads each under a 16-CPU quota) is bounded by exactly those core-seconds.  Read per batch.
 	bool supports_long_join() const override { return true; }
+	bool eqx_regions() const override
+	{
+		const char *e = getenv("MM2AMD_DEVICE_EQX"); // =0: --eqx reads take the host's rounds and the host's mm_update_cigar_eqx, as before cigar_eqx_kernel (A/B checks)
+		return !(e && *e == '0');
+	}
+	// MM_F_EQX (cigar_eqx.hpp) for regions region_finish_kernel has just finished on the lane's stream: count, place (the host waits for the counts: the
+	// pool is sized from their sum), write.  The copy of the pool is queued; the caller waits for the stream.
+	EqxOut eqx_pass(Lane &ln, Lane::EqxBufs &B, KernelProfiler &kp, const FinRegion *d_regions, size_t n, const FinResult *d_res, const uint32_t *d_fin_pool, size_t fin_words, const uint8_t *d_qpool)
+	{
+		hipStream_t st = ln.stream;
+		EqxParams P{};
+		P.regions = d_regions, P.n_regions = (int)n, P.results = d_res, P.fin_pool = d_fin_pool, P.qpool = d_qpool, P.S = T_->S.p;
+		P.n_ops = B.d_n.ensure(n), P.out_off = B.d_off.ensure(n);
+		uint32_t *hn = B.h_n.ensure(n);
+		uint64_t *ho = B.h_off.ensure(n + 1);
+		const double rec_bytes = (double)n * (sizeof(FinRegion) + sizeof(FinResult) + 4);
+		kp.begin(st);
+		cigar_eqx_launch(P, false, st);
+		kp.end(st, "cigar_eqx_kernel[count]", (double)fin_words * 4.0 + rec_bytes, (double)n); // (the sequences' share: eqx_sequence_bytes)
+		HIP_CHECK(hipMemcpyAsync(hn, B.d_n.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+		stream_wait(st);
+		uint64_t total = 0;
+		for (size_t i = 0; i < n; ++i) ho[i] = total, total += hn[i];
+		ho[n] = total;
+		HIP_CHECK(hipMemcpyAsync(B.d_off.p, ho, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+		P.out_pool = B.d_out.ensure(total + 1);
+		uint32_t *hout = B.h_out.ensure(total + 1);
+		kp.begin(st);
+		cigar_eqx_launch(P, true, st);
+		kp.end(st, "cigar_eqx_kernel[write]", ((double)fin_words + (double)total) * 4.0 + rec_bytes + (double)n * 8.0, (double)n);
+		if (total) HIP_CHECK(hipMemcpyAsync(hout, B.d_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+		EqxOut o;
+		o.n_ops = hn, o.off = ho, o.cigars = hout;
+		return o;
+	}
+	// the columns the two passes read, known once the regions' records are on the host: a query byte and half a byte of packed reference per
+	// column, in both passes; a region relabelled in place is not read again by the writing pass
+	void eqx_sequence_bytes(KernelProfiler &kp, const EqxOut &x, const FinRegion *regions, const FinResult *res, size_t n)
+	{
+		if (!x.n_ops || !KernelProfiler::enabled_flag()) return;
+		double cnt = 0, wr = 0;
+		for (size_t i = 0; i < n; ++i) {
+			if (res[i].n_cigar <= 0) continue;
+			const double b = (double)regions[i].q_len + 0.5 * (double)regions[i].t_len;
+			cnt += b;
+			if (x.n_ops[i] != (uint32_t)res[i].n_cigar) wr += 2.0 * b;
+		}
+		kp.add_bytes("cigar_eqx_kernel[count]", cnt), kp.add_bytes("cigar_eqx_kernel[write]", wr);
+	}
 	bool finishes_regions() const override
 	{
 		// Round 4: on by default.  The kernel costs 18 ms per 1-Gbase step (round 3: 56) and takes 1.5 host core-seconds per step off the host (5.5 -> 3.9):
@@ -929,7 +982,7 @@ public:
 		return true;
 	}
 	void finish_regions(int lane_id, const std::vector<FinRegion> &regions, const std::vector<FinPiece> &pieces, size_t out_words, const int8_t *mat25, int q, int e, bool log_gap,
-	                    std::vector<FinResult> &results, const uint32_t **cigars) override
+	                    std::vector<FinResult> &results, const uint32_t **cigars, EqxOut *eqx) override
 	{
 		HIP_CHECK(hipSetDevice(dev_));
 		Lane &ln = *lanes_.at(lane_id);
@@ -955,11 +1008,13 @@ public:
 		prof.begin(ln.stream);
 		region_finish_launch(P, ln.stream);
 		prof.end(ln.stream, "region_finish_kernel", (double)out_words * 8.0 + (double)n * (sizeof(FinRegion) + sizeof(FinResult)), (double)n);
+		if (eqx) *eqx = eqx_pass(ln, ln.eqx_fin, prof, ln.d_fin_regions.p, n, ln.d_fin_res.p, ln.d_fin_out.p, out_words, res_[ln.set].d_qpool.p);
 		HIP_CHECK(hipMemcpyAsync(ln.h_fin_res.p, ln.d_fin_res.p, n * sizeof(FinResult), hipMemcpyDeviceToHost, ln.stream));
 		HIP_CHECK(hipMemcpyAsync(ln.h_fin_out.p, ln.d_fin_out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ln.stream));
 		stream_wait(ln.stream);
 		memcpy(results.data(), ln.h_fin_res.p, n * sizeof(FinResult));
 		*cigars = ln.h_fin_out.p;
+		if (eqx) eqx_sequence_bytes(prof, *eqx, regions.data(), results.data(), n);
 		static const bool check = getenv("MM2AMD_FIN_CHECK") != nullptr; // diagnostic: every returned CIGAR must cover its windows
 		if (check)
 			for (size_t i = 0; i < n; ++i) {

@@ -9,6 +9,7 @@
 #include "ksw_host.hpp"
 #include "kernel_prof.hpp"
 #include "region_finish.hpp"
+#include "cigar_eqx.hpp"
 #include "aln_text.hpp"
 #include "ksw_ll.hpp"
 #include "sdust.hpp"
@@ -229,8 +230,9 @@ int mm2amd_ksw_exts2_batch(int n_jobs, const mm2amd_ksw_job_t *jobs, int8_t m, c
 	return ksw_batch(2, noncan, n_jobs, jobs, m, mat, gapo, gape, gapo2, 0, res, cigar_pool, cigar_pool_cap);
 }
 
-int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
-                              mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap)
+// mm2amd_update_extra_batch, and with eqx mm2amd_update_extra_eqx_batch: cigar_eqx_kernel on top, its pool sized by a first call without one
+static int update_extra_impl(bool eqx, int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
+                             mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap)
 {
 	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat25) return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: bad arguments");
 	if (n_jobs == 0) return 0;
@@ -261,7 +263,7 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
 			out_words += sum;
 			qtot += ((size_t)j.qlen + 15) & ~(size_t)7, ttot += ((size_t)j.tlen + 15) & ~(size_t)7; // (the kernel reads aligned 8-byte / 8-code blocks)
 		}
-		if (out_words > cigar_pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_batch: cigar_pool too small (the sum of the piece lengths suffices)");
+		if (!eqx && out_words > cigar_pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_batch: cigar_pool too small (the sum of the piece lengths suffices)");
 		std::vector<uint8_t> hq(qtot + 16, 0);
 		std::vector<uint32_t> hS(ttot / 8 + 4, 0);
 		for (int i = 0; i < n_jobs; ++i) {
@@ -288,6 +290,44 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
 		P.cap_ops = (int)std::min<uint32_t>((longest + 63) & ~63u, (uint32_t)kFinMaxOps);
 		region_finish_launch(P, dc.stream);
 		std::vector<FinResult> hr(n_jobs);
+		if (eqx) { // count, place, write (cigar_eqx.hpp); cigar_pool null: the counts alone
+			DevBuf<uint32_t> d_n, d_eqx;
+			DevBuf<uint64_t> d_off;
+			EqxParams X{};
+			X.regions = d_regs.p, X.n_regions = n_jobs, X.results = d_res.p, X.fin_pool = d_out.p, X.qpool = d_q.p, X.S = d_S.p;
+			X.n_ops = d_n.ensure(n_jobs), X.out_off = d_off.ensure(n_jobs);
+			KernelProfiler &prof = kernel_profiler();
+			prof.begin(dc.stream);
+			cigar_eqx_launch(X, false, dc.stream);
+			prof.end(dc.stream, "cigar_eqx_kernel[count]", (double)out_words * 4.0 + (double)qtot + (double)ttot / 2 + (double)n_jobs * (sizeof(FinRegion) + sizeof(FinResult) + 4), (double)n_jobs);
+			std::vector<uint32_t> hn(n_jobs);
+			std::vector<uint64_t> hoff(n_jobs);
+			HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(FinResult), hipMemcpyDeviceToHost, dc.stream));
+			HIP_CHECK(hipMemcpyAsync(hn.data(), d_n.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, dc.stream));
+			HIP_CHECK(hipStreamSynchronize(dc.stream));
+			uint64_t total = 0;
+			for (int i = 0; i < n_jobs; ++i) {
+				const FinResult &f = hr[i];
+				mm2amd_fin_res_t &o = res[i];
+				o.n_cigar = f.n_cigar < 0 ? f.n_cigar : (int32_t)hn[i], o.blen = f.blen, o.mlen = f.mlen, o.n_ambi = f.n_ambi, o.dp_max = f.dp_max, o.qshift = f.qshift, o.tshift = f.tshift;
+				o.is_spliced = f.is_spliced, o.cigar_off = (uint32_t)total;
+				hoff[i] = total, total += hn[i];
+			}
+			if (total >= (1ull << 32)) { prof.collect(); return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_eqx_batch: the batch's =/X CIGARs exceed 32-bit offsets"); }
+			if (!cigar_pool) { prof.collect(); return 0; }
+			if (total > cigar_pool_cap) { prof.collect(); return fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_eqx_batch: cigar_pool too small (a call with cigar_pool == NULL gives every res[i].n_cigar)"); }
+			HIP_CHECK(hipMemcpyAsync(d_off.p, hoff.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, dc.stream));
+			X.out_pool = d_eqx.ensure(total + 1);
+			prof.begin(dc.stream);
+			cigar_eqx_launch(X, true, dc.stream);
+			prof.end(dc.stream, "cigar_eqx_kernel[write]", ((double)out_words + (double)total) * 4.0 + 2.0 * ((double)qtot + (double)ttot / 2) + (double)n_jobs * (sizeof(FinRegion) + sizeof(FinResult) + 12), (double)n_jobs);
+			std::vector<uint32_t> he(total + 1);
+			if (total) HIP_CHECK(hipMemcpyAsync(he.data(), d_eqx.p, total * 4, hipMemcpyDeviceToHost, dc.stream));
+			HIP_CHECK(hipStreamSynchronize(dc.stream));
+			prof.collect();
+			if (total) memcpy(cigar_pool, he.data(), total * 4);
+			return 0;
+		}
 		std::vector<uint32_t> ho(out_words + 1);
 		HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(FinResult), hipMemcpyDeviceToHost, dc.stream));
 		if (out_words) HIP_CHECK(hipMemcpyAsync(ho.data(), d_out.p, out_words * 4, hipMemcpyDeviceToHost, dc.stream));
@@ -301,6 +341,18 @@ int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const in
 		if (out_words) memcpy(cigar_pool, ho.data(), out_words * 4);
 		return 0;
 	});
+}
+
+int mm2amd_update_extra_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
+                              mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap)
+{
+	return update_extra_impl(false, n_jobs, jobs, mat25, q, e, log_gap, res, cigar_pool, cigar_pool_cap);
+}
+
+int mm2amd_update_extra_eqx_batch(int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
+                                  mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap)
+{
+	return update_extra_impl(true, n_jobs, jobs, mat25, q, e, log_gap, res, cigar_pool, cigar_pool_cap);
 }
 
 int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)

@@ -40,12 +40,12 @@ double thr_now() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); ret
 
 // Backend::align_regions takes single-segment reads of the plain long-read configurations: dual- or single-affine DNA alignment with CIGARs.  What it leaves
 // to the host path -- each a rule the device kernels do not carry: spliced and short-read alignment (two strands per region, ungapped shortcuts, composed
-// targets), query-strand coordinates, =/X CIGARs, chains reported as hits, ALT contigs, junction / jump annotation, and the re-seeding of reads without chains
+// targets), query-strand coordinates, chains reported as hits, ALT contigs, junction / jump annotation, and the re-seeding of reads without chains
 // (-f x,y: map.c:293-316).
 bool region_path_supported(const MapOpt &opt, int idx_flag, int n_alt, bool has_annotation)
 {
 	if (!(opt.flag & F_CIGAR)) return false;
-	if (opt.flag & (F_SPLICE | F_SR_RNA | F_QSTRAND | F_EQX | F_ALL_CHAINS)) return false;
+	if (opt.flag & (F_SPLICE | F_SR_RNA | F_QSTRAND | F_ALL_CHAINS)) return false;
 	if (n_alt > 0 || has_annotation) return false;
 	(void)idx_flag; // (round 5, late: homopolymer-compressed indices take the device path too -- region_plan_kernel's window boundaries, the summed minimizer spans)
 	// (round 6: short reads and their pairs take the device path -- the best diagonal run, the ungapped window, the fragment's chains cut per segment)
@@ -251,7 +251,8 @@ std::shared_ptr<Mapper::BatchRun> Mapper::make_run(int set)
 	if (const char *e = getenv("MM2AMD_ACTIVE_LANES")) n_drivers = std::max(1, std::min(n_drivers, atoi(e))); // read per run: bench.py takes its un-overlapped kernel times with one lane
 	b.n_drivers = n_drivers;
 	b.device_finish = be_.finishes_regions(); // one answer for the whole batch
-	b.device_regions = rgn_ok_ && b.device_finish && be_.aligns_regions();
+	b.device_eqx = (opt_.flag & F_EQX) && b.device_finish && be_.eqx_regions(); // (cigar_eqx_kernel; MM2AMD_DEVICE_EQX=0: the host's mm_update_cigar_eqx, from the host's rounds)
+	b.device_regions = rgn_ok_ && b.device_finish && be_.aligns_regions() && (!(opt_.flag & F_EQX) || b.device_eqx);
 	return bp;
 }
 
@@ -295,7 +296,7 @@ void Mapper::driver_loop(int lane)
 			DriverScratch &ds = *scratch_.at(lane);
 			std::vector<std::unique_ptr<Aligner>> &al = ds.al;
 			if (al.empty()) { al.resize(n_threads_); for (auto &p : al) p.reset(new Aligner(opt_, fi_)); }
-			for (auto &p : al) p->device_finish(b->device_finish);
+			for (auto &p : al) p->device_finish(b->device_finish, b->device_eqx);
 			process_sub(*b, b->subs[si].first, b->subs[si].second, lane, al, ds, st);
 		} catch (...) {
 			err = std::current_exception();
@@ -362,6 +363,8 @@ void Mapper::device_hits(const Backend::RegionBatchOut &rb, const ReadChains &c,
 		if (rb.plan[slot].status != 0 || rb.fin_res[slot].n_cigar < 0 || (uint32_t)rb.fin_res[slot].n_cigar + kHdr > rb.plan[slot].capacity)
 			throw std::runtime_error("[mm2amd] align_regions: a finished region without a consistent CIGAR");
 	}
+	const bool eqx = (opt_.flag & F_EQX) != 0; // the CIGAR handed on is cigar_eqx_kernel's, the container what mm_update_cigar_eqx leaves (align.c:209-221)
+	if (eqx && !rb.eqx.n_ops) throw std::runtime_error("[mm2amd] align_regions: --eqx regions came back without their =/X CIGARs");
 	for (int32_t p = 0; p < ro.n_regs; ++p) {
 		const uint32_t slot = ro.reg0 + (uint32_t)p;
 		Reg r = rb.regs[slot];
@@ -369,12 +372,14 @@ void Mapper::device_hits(const Backend::RegionBatchOut &rb, const ReadChains &c,
 		const RgnPlan &pl = rb.plan[slot];
 		const FinResult &f = rb.fin_res[slot];
 		r.div = x.n_tot < 0 ? -1.0f : x.n_match >= x.n_tot ? 0.0f : (float)(1.0 - pow((double)x.n_match / x.n_tot, 1.0 / avg_k)); // esterr.c:61
-		r.p = (Extra *)malloc((size_t)pl.capacity * 4); // (the header is set below, the operations copied; what lies beyond them is as undefined as after the reference's realloc)
+		const uint32_t n_cigar = eqx ? rb.eqx.n_ops[slot] : (uint32_t)f.n_cigar;
+		const uint32_t capacity = eqx ? eqx_capacity(pl.capacity, (uint32_t)f.n_cigar, n_cigar, (uint32_t)sizeof(Extra)) : pl.capacity; // (>= n_cigar + kHdr: the header's bytes are added to a word count)
+		r.p = (Extra *)malloc((size_t)capacity * 4); // (the header is set below, the operations copied; what lies beyond them is as undefined as after the reference's realloc)
 		if (!r.p) { for (Reg &done : regs) free(done.p); regs.clear(); throw std::bad_alloc(); }
 		memset(r.p, 0, sizeof(Extra));
-		r.p->capacity = pl.capacity;
-		r.p->n_cigar = (uint32_t)f.n_cigar;
-		memcpy(r.p->cigar, rb.cigars + rb.fin[slot].out_off, (size_t)f.n_cigar * 4);
+		r.p->capacity = capacity;
+		r.p->n_cigar = n_cigar;
+		memcpy(r.p->cigar, eqx ? rb.eqx.cigars + rb.eqx.off[slot] : rb.cigars + rb.fin[slot].out_off, (size_t)n_cigar * 4);
 		r.p->dp_score = pl.dp_score, r.p->dp_max = r.p->dp_max0 = f.dp_max, r.p->n_ambi = (uint32_t)f.n_ambi;
 		r.blen = f.blen, r.mlen = f.mlen, r.is_spliced = f.is_spliced;
 		if (f.qshift) { if (r.rev) r.qe -= f.qshift; else r.qs += f.qshift; } // mm_fix_cigar's dropped leading gap (align.c:171-180)
@@ -704,9 +709,14 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 						}
 					}, 256);
 					const uint32_t *fin_cigars = nullptr;
-					be_.finish_regions(lane, fregs, fpieces, out_words, aligner.mat(), opt_.q, opt_.e, !(opt_.flag & (F_SR | F_SR_RNA)), ds.fin_results, &fin_cigars);
+					EqxOut eqx;
+					be_.finish_regions(lane, fregs, fpieces, out_words, aligner.mat(), opt_.q, opt_.e, !(opt_.flag & (F_SR | F_SR_RNA)), ds.fin_results, &fin_cigars, batch.device_eqx ? &eqx : nullptr);
+					if (batch.device_eqx && !eqx.n_ops) throw std::runtime_error("[mm2amd] finish_regions: --eqx regions came back without their =/X CIGARs");
 					parallel_for(n_threads_, mu, [&](long i, int tid) {
-						if (!ra[i].finish_queue.empty()) active[i] = al[tid]->complete_finished(ra[i], ds.fin_results.data() + fbase[i], fregs.data() + fbase[i], fin_cigars) ? 1 : 0;
+						if (ra[i].finish_queue.empty()) return;
+						EqxOut mine = eqx; // (the unit's regions are the first of the views it is given)
+						if (mine.n_ops) mine.n_ops += fbase[i], mine.off += fbase[i];
+						active[i] = al[tid]->complete_finished(ra[i], ds.fin_results.data() + fbase[i], fregs.data() + fbase[i], fin_cigars, mine) ? 1 : 0;
 					});
 				}
 			}

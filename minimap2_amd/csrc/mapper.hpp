@@ -85,7 +85,7 @@ private:
 	// One batch on its way through the lanes: its resident set (ours and the backend's), its sub-batches and who has taken them, its results.
 	struct BatchRun {
 		int set = 0, be_set = 0, n_drivers = 1;
-		bool device_finish = false, device_regions = false, cancelled = false;
+		bool device_finish = false, device_regions = false, device_eqx = false, cancelled = false;
 		SeedChainParams sp;
 		std::vector<std::pair<long, long>> subs;
 		size_t next_sub = 0, n_done = 0, n_taken = 0; // guarded by mu_
