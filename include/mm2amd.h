@@ -281,6 +281,16 @@ int mm2amd_idx_getseq(const mm2amd_index_t *idx, uint32_t rid, uint32_t st, uint
  * index without sequence, rid / rs / re outside the sequence, or qs / qe outside the read. */
 int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *const *hit, const char *const *qseq, const int32_t *qlen,
                            int what, int is_qstrand, mm2amd_txt_res_t *res, char *pool, size_t pool_cap);
+/* mm_write_junc (format.c:263-300) for a batch of hits: the splice junctions of hit[i] -- an mm_reg1_t* -- of the read named qname[i], one line
+ * tname \t start \t end \t qname \t score \t +|-  per intron (N operation), as the reference leaves them in its kstring: joined by '\n', none at
+ * the end.  A hit that writes nothing (not is_spliced, p == NULL, trans_strand neither 1 nor 2, no intron) gets len 0, status 0.  There is no
+ * mapq / parent filter here: that is map.c's (:604).  junc_text_kernel, one wavefront per hit that can write; the target comes from the handle's
+ * packed sequence on the device.  res and pool as for mm2amd_aln_text_batch (pool == NULL sizes the batch; a pool too small: MM2AMD_ENOMEM, the
+ * lengths filled, nothing written).  A hit whose CIGAR breaks the reference's asserts (an intron shorter than 2, a walk that does not end at re)
+ * or holds an operation code above 9 gets status -1 and no text, and the call succeeds.  MM2AMD_EINVAL for an index without names
+ * (MM_I_NO_NAME) or without sequence, or for rid / rs / re outside the sequence. */
+int mm2amd_hits_junc_batch(const mm2amd_index_t *idx, int n_hits, const void *const *hit, const char *const *qname, mm2amd_txt_res_t *res,
+                           char *pool, size_t pool_cap);
 /* Diagnostics: the phases of this process' last mm2amd_idx_dump / mm2amd_idx_load -- total, regroup (dump: sort by bucket + offsets), serialise / unpack
  * kernels, device<->host copies (HIP events), file write / read (host clock), sort and tables (load), of which S, then image bytes, file bytes, chunks,
  * chunk bytes.  Milliseconds and bytes; returns the number of values there are. */
@@ -350,7 +360,11 @@ void mm_gpu_batch_discard(void);                 /* drop a staged batch that wil
  * Arguments as for mm_gpu_map_batch (results as it returned them); *out receives ONE malloc'd block of '\n'-terminated
  * records in input order (free() it), *out_len its length.  Fragments of one or two segments (mate fields of mm_write_sam3,
  * /1 /2 names of mm_write_paf4); no RG tag; uses the index and
- * options given to mm_gpu_init. */
+ * options given to mm_gpu_init.
+ * With MM_F_OUT_JUNC (--write-junc) the text is that of map.c:601-607 instead: for every hit with id == parent and mapq >= 10, mm_write_junc's
+ * lines (format.c:263-300: tname \t start \t end \t qname \t score \t +|- per intron), each with its '\n'; nothing for other hits or for reads
+ * without hits; the SAM / PAF flags play no part.  MM2AMD_EINVAL, and no text, for an index without names or without sequence, or when such a hit's
+ * CIGAR breaks the reference's asserts (an intron shorter than 2, operations that do not end at re) or holds an operation code above 9. */
 int mm_gpu_format_batch(int n_frag, const int *seg_off, const int *n_seg, MM2AMD_BSEQ_PTR seq, const int *n_reg, void *const *reg,
                         const int *rep_len, char **out, size_t *out_len);
 /* The same text in a buffer the library owns and reuses: *out stays valid until the next mm_gpu_format_batch_view call (or mm_gpu_destroy);
@@ -369,7 +383,9 @@ int mm_gpu_format_batch_view(int n_frag, const int *seg_off, const int *n_seg, M
  * set, MM_F_COPY_COMMENT is set and a comment is present, a record's CIGAR has to go into the CG:B:I tag (MM_F_LONG_CIGAR, more than 65535
  * operations), a de / dv value lies outside [0, 1], or cs / MD is asked of an index without sequence.  Everything else, an empty batch
  * included, is written by the device.  MM2AMD_DEVICE_TEXT=1 in the environment routes mm_gpu_format_batch and mm_gpu_format_batch_view
- * through the same path (unset or 0: the host writer, as ever). */
+ * through the same path (unset or 0: the host writer, as ever).
+ * With MM_F_OUT_JUNC the junction lines are written by junc_text_kernel (one wavefront per hit that prints), for fragments of one and of two
+ * segments alike and whatever the other flags; the device is the path also for a batch that prints nothing. */
 #define MM2AMD_FMT_PATH_DEVICE 0
 #define MM2AMD_FMT_PATH_HOST   1
 int mm_gpu_format_batch_dev(int n_frag, const int *seg_off, const int *n_seg, MM2AMD_BSEQ_PTR seq, const int *n_reg, void *const *reg,

@@ -117,6 +117,7 @@ assert C.sizeof(MapOpt) == 264 and C.sizeof(Reg1) == 80 and C.sizeof(Extra) == 2
 
 F_CIGAR, F_OUT_SAM = 0x004, 0x008  # MM_F_CIGAR, MM_F_OUT_SAM (minimap.h:12-13)
 F_EQX = 0x4000000  # MM_F_EQX (minimap.h:36): --eqx, match operations written as = and X
+F_OUT_JUNC = 0x10000000000  # MM_F_OUT_JUNC (minimap.h:50): --write-junc, the splice junctions of the hits instead of SAM / PAF records
 I_HPC, I_NO_SEQ, I_NO_NAME = 1, 2, 4  # MM_I_* (minimap.h:41-43)
 EINVAL, ENODEV, EHIP, ENOMEM, ESTATE, EIO = -1, -2, -3, -4, -5, -6  # MM2AMD_E*
 DUMP_NO_SEQ = 1  # MM2AMD_DUMP_NO_SEQ
@@ -165,6 +166,7 @@ def _bind(L):
         L.mm2amd_aln_text_batch.argtypes = [C.c_int, C.POINTER(TxtJob), C.c_int, C.POINTER(TxtRes), vp, C.c_size_t]
         L.mm2amd_hits_text_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(TxtRes), vp,
                                              C.c_size_t]
+        L.mm2amd_hits_junc_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_char_p), C.POINTER(TxtRes), vp, C.c_size_t]
         L.mm2amd_idx_getseq.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         if hasattr(L, "mm2amd_ksw_ll_batch"):
             L.mm2amd_ksw_ll_batch.argtypes = [C.c_int, C.POINTER(LlJob), C.c_int8, C.c_char_p, C.c_int, C.c_int, C.POINTER(LlRes)]
@@ -473,6 +475,17 @@ def hits_text(idx, hits, reads, what, is_qstrand=False):
     return _texts(lambda res, pool, cap: L.mm2amd_hits_text_batch(idx, n, harr, qarr, qlen, what, 1 if is_qstrand else 0, res, pool, cap), n)
 
 
+def hits_junc(idx, hits, names):
+    """mm2amd_hits_junc_batch: idx an index handle, hits the addresses of mm_reg1_t records, names each hit's read name.  Returns each hit's
+    junction lines as mm_write_junc (format.c:263-300) leaves them -- joined by '\\n', none at the end; '' for a hit that writes nothing, None
+    for one whose CIGAR the kernel refuses."""
+    n = len(hits)
+    harr = (C.c_void_p * max(n, 1))(*hits)
+    narr = (C.c_char_p * max(n, 1))(*[x.encode() if isinstance(x, str) else bytes(x) for x in names])
+    L = lib()
+    return _texts(lambda res, pool, cap: L.mm2amd_hits_junc_batch(idx, n, harr, narr, res, pool, cap), n)
+
+
 def sort_pairs_u64(keys, vals, bits=64):
     """(keys, vals) -- numpy uint64 arrays of equal length -- sorted by key bits [0, bits), stably, on the device (the index build's sort,
     device_sort.hip).  Returns new arrays."""
@@ -655,13 +668,15 @@ class Aligner(object):
     there is more than one; the file's k, w and flags replace the preset's) or FASTA / FASTQ, plain or gzip.  fn_idx_out: write the index there
     as a .mmi (mm2amd_idx_dump) once it is built.  extra_flags: MM_F_* bits ORed into map_opt.flag (mappy's parameter of the same name).
     sdust_thres: minimap2's -T (minimizers lying mostly in SDUST-masked stretches of a read are dropped; 0 = off).  eqx: minimap2's --eqx (MM_F_EQX).
+    write_junc: minimap2's --write-junc (MM_F_OUT_JUNC | MM_F_CIGAR): the text of pipeline(text=True), format_raw() and map_pairs(text=True) is then
+    the splice junctions of the hits (one BED-like line per intron; the input of a second pass with --pass1) instead of SAM / PAF records.
     n_gpus / device_ids: map every batch on several GPUs of this process (mm_gpu_init_index_multi: index replicated, reads sharded
     by bases; an ordinal may repeat).  Only one Aligner can be the active mapper of the process at a time (the drop-in boundary is
     a process-wide context, like the reference's pipeline): creating a second one makes the first inactive -- its map calls raise,
     and closing or collecting it leaves the new context alone."""
 
     def __init__(self, seq=None, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None,
-                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0, eqx=False):
+                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0, eqx=False, write_junc=False):
         L = lib()
         self._generation, self._idx, self._staged = 0, None, None  # close() must work on a half-built object
         self.last_format_path = None  # FMT_PATH_* of the last format_raw(device=True)
@@ -682,6 +697,8 @@ class Aligner(object):
         self.map_opt.flag |= extra_flags  # MM_F_* bits beyond the preset's (mappy.Aligner's extra_flags)
         if eqx:
             self.map_opt.flag |= F_EQX  # minimap2's --eqx
+        if write_junc:
+            self.map_opt.flag |= F_OUT_JUNC | F_CIGAR  # minimap2's --write-junc (main.c)
         if sdust_thres:
             self.map_opt.sdust_thres = sdust_thres
         from_index = fn_idx_in is not None and idx_is_idx(fn_idx_in)

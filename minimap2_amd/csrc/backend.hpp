@@ -11,6 +11,7 @@
 #include "cigar_eqx.hpp"
 #include "region_dev.hpp"
 #include "rec_text.hpp"
+#include "junc_text.hpp"
 
 namespace mm2amd {
 
@@ -117,12 +118,16 @@ public:
 	//   rec_text_begin   pinned buffers of the planned sizes, for the planner to fill;
 	//   rec_text_size    uploads them, runs the sizing pass; returns the records' results (pinned, valid until the next begin);
 	//   rec_text_write   the writing pass at the given offsets (one per record, host memory); returns the device's text (pinned, valid until the next begin).
+	//   junc_text_size / junc_text_write   the same two passes of junc_text_kernel (junc_text.hpp: --write-junc) over tables from rec_text_begin: a job and a hit
+	//                    per printable hit, RecHit::t_pos the first nibble of the hit's sequence in S.
 	struct RecTextSizes { size_t n_jobs = 0, n_hits = 0, name_bytes = 0, q_bytes = 0, cigar_words = 0; };
 	struct RecTextBufs { RecJob *jobs = nullptr; RecHit *hits = nullptr; char *names = nullptr; uint8_t *q = nullptr; uint32_t *cigar = nullptr; uint64_t *off = nullptr; };
 	virtual bool writes_records() const { return false; }
 	virtual RecTextBufs rec_text_begin(const RecTextSizes & /*sz*/) { return RecTextBufs(); }
 	virtual const RecRes *rec_text_size(int64_t /*flag*/) { return nullptr; }
 	virtual const char *rec_text_write(uint64_t /*total*/) { return nullptr; }
+	virtual const RecRes *junc_text_size(int64_t /*flag*/) { return nullptr; }
+	virtual const char *junc_text_write(uint64_t /*total*/) { return nullptr; }
 	virtual bool finishes_regions() const { return false; }
 	virtual void finish_regions(int /*lane*/, const std::vector<FinRegion> & /*regions*/, const std::vector<FinPiece> & /*pieces*/, size_t /*out_words*/, const int8_t * /*mat25*/,
 	                            int /*q*/, int /*e*/, bool /*log_gap*/, std::vector<FinResult> & /*results*/, const uint32_t ** /*cigars*/, EqxOut * /*eqx*/ = nullptr) {}

@@ -1069,7 +1069,14 @@ public:
 		R.h_res.ensure(sz.n_jobs + 1);
 		return b;
 	}
-	const RecRes *rec_text_size(int64_t flag) override
+	const RecRes *rec_text_size(int64_t flag) override { return text_size(flag, false); }
+	const char *rec_text_write(uint64_t total) override { return text_write(total, false); }
+	const RecRes *junc_text_size(int64_t flag) override { return text_size(flag, true); }
+	const char *junc_text_write(uint64_t total) override { return text_write(total, true); }
+
+private:
+	// the two passes of rec_text_kernel, or (junc) of junc_text_kernel, over the tables of rec_text_begin
+	const RecRes *text_size(int64_t flag, bool junc)
 	{
 		HIP_CHECK(hipSetDevice(dev_));
 		RecText &R = rt_;
@@ -1087,14 +1094,14 @@ public:
 		P.tnames = R.d_tnames.p, P.tname_off = R.d_tname_off.p, P.tlen = R.d_tlen.p, P.res = R.d_res.p, P.off = nullptr, P.out = nullptr;
 		KernelProfiler &prof = kernel_profiler(kMaxProfLanes - 1, replica_);
 		prof.begin(R.stream);
-		rec_text_launch(P, false, R.stream);
-		prof.end(R.stream, "rec_text_kernel[size]", (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
+		if (junc) junc_text_launch(P, false, R.stream); else rec_text_launch(P, false, R.stream);
+		prof.end(R.stream, junc ? "junc_text_kernel[size]" : "rec_text_kernel[size]", (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
 		HIP_CHECK(hipMemcpyAsync(R.h_res.p, R.d_res.p, sz.n_jobs * sizeof(RecRes), hipMemcpyDeviceToHost, R.stream));
 		stream_wait(R.stream);
 		prof.collect();
 		return R.h_res.p;
 	}
-	const char *rec_text_write(uint64_t total) override
+	const char *text_write(uint64_t total, bool junc)
 	{
 		HIP_CHECK(hipSetDevice(dev_));
 		RecText &R = rt_;
@@ -1106,15 +1113,14 @@ public:
 		R.P.off = R.d_off.p, R.P.out = R.d_out.p;
 		KernelProfiler &prof = kernel_profiler(kMaxProfLanes - 1, replica_);
 		prof.begin(R.stream);
-		rec_text_launch(R.P, true, R.stream);
-		prof.end(R.stream, "rec_text_kernel[write]", (double)total + (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
+		if (junc) junc_text_launch(R.P, true, R.stream); else rec_text_launch(R.P, true, R.stream);
+		prof.end(R.stream, junc ? "junc_text_kernel[write]" : "rec_text_kernel[write]", (double)total + (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
 		HIP_CHECK(hipMemcpyAsync(R.h_out.p, R.d_out.p, total, hipMemcpyDeviceToHost, R.stream));
 		stream_wait(R.stream);
 		prof.collect();
 		return R.h_out.p;
 	}
 
-private:
 	struct RecText {
 		hipStream_t stream = nullptr;
 		bool targets_ready = false;

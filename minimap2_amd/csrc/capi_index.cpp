@@ -16,11 +16,16 @@
 #include "index_handle.hpp"
 #include "options.hpp"
 #include "aln_text.hpp"
+#include "junc_text.hpp"
+#include <map>
 
 namespace mm2amd {
 int capi_fail(int code, const std::string &msg);
 int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const std::vector<uint8_t> &hq, const std::vector<uint8_t> &ht, const uint32_t *dS,
                  const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool, size_t pool_cap); // capi_kernels.cpp
+int junc_text_run(DeviceCtx &dc, const std::vector<RecJob> &jobs, const std::vector<RecHit> &hits, const std::vector<int> &slot, int n_res, const std::string &names,
+                  const std::string &tnames, const std::vector<uint64_t> &tname_off, const uint32_t *dS, const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool,
+                  size_t pool_cap); // capi_kernels.cpp
 struct IndexHandle {
 	FlatIndex fi;
 	DeviceIndexTables T;
@@ -261,6 +266,57 @@ int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *co
 		std::lock_guard<std::mutex> lk(dc.mu);
 		ensure_device(dc);
 		return aln_text_run(dc, tj, what, hq, ht, h->T.S.p, cig, res, pool, pool_cap);
+	} catch (const HipError &e) {
+		const std::string s = e.what();
+		return capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
+	} catch (const std::exception &e) {
+		return capi_fail(MM2AMD_EINVAL, e.what());
+	}
+}
+
+int mm2amd_hits_junc_batch(const mm2amd_index_t *idx, int n_hits, const void *const *hit, const char *const *qname, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
+{
+	if (!idx) return capi_fail(MM2AMD_EINVAL, "[mm2amd] null index");
+	if (n_hits < 0 || (n_hits > 0 && (!hit || !qname || !res))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: bad arguments");
+	const IndexHandle *h = (const IndexHandle *)idx;
+	const FlatIndex &fi = h->fi;
+	if (fi.flag & ref::I_NO_NAME) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: the index holds no sequence names");
+	if ((fi.flag & ref::I_NO_SEQ) || !fi.S || !h->T.S.p) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: the index holds no sequence");
+	if (n_hits == 0) return 0;
+	try {
+		std::vector<RecJob> jobs;
+		std::vector<RecHit> hits;
+		std::vector<int> slot;
+		std::vector<uint32_t> cig;
+		std::string names, tnames;
+		std::vector<uint64_t> tname_off(1, 0);
+		std::map<int32_t, int32_t> tslot; // rid -> its name's place in tname_off
+		for (int i = 0; i < n_hits; ++i) {
+			const ref::Reg1 *r = (const ref::Reg1 *)hit[i];
+			if (!r || !qname[i]) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: null hit or name");
+			if (!r->is_spliced || !r->p || (r->p->trans_strand != 1 && r->p->trans_strand != 2)) continue; // format.c:267-268
+			if (r->rid < 0 || (uint32_t)r->rid >= fi.n_seq || r->rs < 0 || r->rs > r->re || (uint32_t)r->re > fi.seq_len[r->rid])
+				return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: a hit lies outside its reference sequence");
+			auto ts = tslot.find(r->rid);
+			if (ts == tslot.end()) {
+				ts = tslot.emplace(r->rid, (int32_t)tname_off.size() - 1).first;
+				tnames += fi.names[r->rid], tname_off.push_back(tnames.size());
+			}
+			RecHit o;
+			memset(&o, 0, sizeof o);
+			o.rid = ts->second, o.rs = r->rs, o.re = r->re, o.qs = r->qs, o.qe = r->qe, o.n_cigar = r->p->n_cigar, o.cig_off = cig.size(), o.t_pos = fi.seq_off[r->rid];
+			o.bits = r->mapq | (r->rev ? kRecRev : 0u) | kRecHasP | kRecIsSpliced | (r->id == r->parent ? kRecIsParent : 0u) | (uint32_t)r->p->trans_strand << kRecTransShift;
+			RecJob J;
+			memset(&J, 0, sizeof J);
+			J.name_off = names.size(), J.name_len = (uint32_t)strlen(qname[i]), J.rep_len = -1, J.hit = (int32_t)hits.size(), J.hit0 = (uint32_t)hits.size(), J.n_hits = 1;
+			names.append(qname[i], J.name_len);
+			cig.insert(cig.end(), r->p->cigar, r->p->cigar + r->p->n_cigar);
+			jobs.push_back(J), hits.push_back(o), slot.push_back(i);
+		}
+		DeviceCtx &dc = device_ctx(h->device);
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		return junc_text_run(dc, jobs, hits, slot, n_hits, names, tnames, tname_off, h->T.S.p, cig, res, pool, pool_cap);
 	} catch (const HipError &e) {
 		const std::string s = e.what();
 		return capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);

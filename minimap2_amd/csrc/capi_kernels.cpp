@@ -11,6 +11,7 @@
 #include "region_finish.hpp"
 #include "cigar_eqx.hpp"
 #include "aln_text.hpp"
+#include "junc_text.hpp"
 #include "ksw_ll.hpp"
 #include "sdust.hpp"
 #include "sdust_core.hpp"
@@ -140,6 +141,66 @@ int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const
 	prof.begin(dc.stream);
 	aln_text_launch(P, true, dc.stream);
 	prof.end(dc.stream, "aln_text_kernel[write]", (double)total, cols);
+	HIP_CHECK(hipMemcpyAsync(pool, d_out.p, total, hipMemcpyDeviceToHost, dc.stream));
+	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	prof.collect();
+	return 0;
+}
+
+// The two passes of junc_text_kernel for mm2amd_hits_junc_batch (capi_index.cpp); the caller holds dc.mu and has made the device current.
+// jobs / hits: one of each per hit that can write, in hit order; slot[k]: the hit's place in res (n_res entries, the others get len 0, status 0);
+// names / tnames: the read and target names the jobs and hits point into (hits[k].rid indexes tname_off); dS: the handle's packed sequence.
+int junc_text_run(DeviceCtx &dc, const std::vector<RecJob> &jobs, const std::vector<RecHit> &hits, const std::vector<int> &slot, int n_res, const std::string &names,
+                  const std::string &tnames, const std::vector<uint64_t> &tname_off, const uint32_t *dS, const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool,
+                  size_t pool_cap)
+{
+	const int n_jobs = (int)jobs.size();
+	for (int i = 0; i < n_res; ++i) res[i].off = 0, res[i].len = 0, res[i].status = 0;
+	if (n_jobs == 0) return 0;
+	DevBuf<RecJob> d_jobs;
+	DevBuf<RecHit> d_hits;
+	DevBuf<char> d_names, d_tnames, d_out;
+	DevBuf<uint64_t> d_tname_off, d_off;
+	DevBuf<uint32_t> d_cig;
+	DevBuf<RecRes> d_res;
+	d_jobs.ensure(n_jobs), d_hits.ensure(n_jobs), d_names.ensure(names.size() + 1), d_tnames.ensure(tnames.size() + 1), d_tname_off.ensure(tname_off.size()), d_cig.ensure(cig.size() + 1);
+	d_res.ensure(n_jobs), d_off.ensure(n_jobs);
+	HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)n_jobs * sizeof(RecJob), hipMemcpyHostToDevice, dc.stream));
+	HIP_CHECK(hipMemcpyAsync(d_hits.p, hits.data(), (size_t)n_jobs * sizeof(RecHit), hipMemcpyHostToDevice, dc.stream));
+	if (!names.empty()) HIP_CHECK(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, dc.stream));
+	if (!tnames.empty()) HIP_CHECK(hipMemcpyAsync(d_tnames.p, tnames.data(), tnames.size(), hipMemcpyHostToDevice, dc.stream));
+	HIP_CHECK(hipMemcpyAsync(d_tname_off.p, tname_off.data(), tname_off.size() * 8, hipMemcpyHostToDevice, dc.stream));
+	if (!cig.empty()) HIP_CHECK(hipMemcpyAsync(d_cig.p, cig.data(), cig.size() * 4, hipMemcpyHostToDevice, dc.stream));
+	RecParams P{};
+	P.jobs = d_jobs.p, P.n_jobs = n_jobs, P.hits = d_hits.p, P.flag = 0, P.names = d_names.p, P.qpool = nullptr, P.S = dS, P.cigar = d_cig.p;
+	P.tnames = d_tnames.p, P.tname_off = d_tname_off.p, P.tlen = nullptr, P.res = d_res.p, P.off = nullptr, P.out = nullptr;
+	KernelProfiler &prof = kernel_profiler(0);
+	prof.begin(dc.stream);
+	junc_text_launch(P, false, dc.stream);
+	prof.end(dc.stream, "junc_text_kernel[size]", (double)cig.size() * 4.0, (double)n_jobs);
+	std::vector<RecRes> hr(n_jobs);
+	HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(RecRes), hipMemcpyDeviceToHost, dc.stream));
+	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	std::vector<uint64_t> off(n_jobs);
+	uint64_t total = 0;
+	for (int k = 0, i = 0; i < n_res; ++i) {
+		res[i].off = total;
+		if (k < n_jobs && slot[k] == i) {
+			off[k] = total, res[i].len = hr[k].len, res[i].status = hr[k].status == kRecOk ? 0 : -1;
+			total += hr[k].len, ++k;
+		}
+	}
+	if (!pool || total > pool_cap || total == 0) {
+		prof.collect();
+		if (pool && total > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] junction text: pool too small (a call with pool == NULL gives the lengths)");
+		return 0;
+	}
+	d_out.ensure(total, 1.0);
+	HIP_CHECK(hipMemcpyAsync(d_off.p, off.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, dc.stream));
+	P.off = d_off.p, P.out = d_out.p;
+	prof.begin(dc.stream);
+	junc_text_launch(P, true, dc.stream);
+	prof.end(dc.stream, "junc_text_kernel[write]", (double)total + (double)cig.size() * 4.0, (double)n_jobs);
 	HIP_CHECK(hipMemcpyAsync(pool, d_out.p, total, hipMemcpyDeviceToHost, dc.stream));
 	HIP_CHECK(hipStreamSynchronize(dc.stream));
 	prof.collect();

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 #include "format.hpp"
@@ -303,6 +304,62 @@ void put_paf(Text &o, const FlatIndex &fi, const Bseq1 &t, const Reg1 *r, int64_
 	if ((flag & F_COPY_COMMENT) && t.comment) o.ch('\t'), o.str(t.comment);
 }
 
+// --write-junc (map.c:601-607): the hits whose junctions are printed -- map.c's filter and the three tests of mm_write_junc (format.c:267-268)
+bool junc_printable(const Reg1 &r)
+{
+	return r.id == r.parent && r.mapq >= 10 && r.is_spliced && r.p && (r.p->trans_strand == 1 || r.p->trans_strand == 2);
+}
+// an index mm_write_junc cannot print from (it would read a null name or no sequence)
+void junc_index_check(const FlatIndex &fi)
+{
+	if (fi.flag & I_NO_NAME) throw std::invalid_argument("[mm2amd] --write-junc: the index holds no sequence names");
+	if ((fi.flag & I_NO_SEQ) || !fi.S) throw std::invalid_argument("[mm2amd] --write-junc: the index holds no sequence");
+}
+// ... and a printable hit it cannot print (what the kernel indexes with; the CIGAR is the walk's business)
+void junc_hit_check(const FlatIndex &fi, const Bseq1 &t, const Reg1 &r)
+{
+	if (!t.name) throw std::invalid_argument("[mm2amd] --write-junc: a read without a name");
+	if (r.rid < 0 || (uint32_t)r.rid >= fi.n_seq || r.rs < 0 || r.rs > r.re || (uint32_t)r.re > fi.seq_len[r.rid])
+		throw std::invalid_argument("[mm2amd] --write-junc: a hit lies outside its reference sequence");
+}
+const char kJuncBadCigar[] = "[mm2amd] --write-junc: a hit's CIGAR holds an intron shorter than 2, an unknown operation, or does not end at the hit's end";
+
+// mm_write_junc (format.c:263-300) for a printable hit, every line with its \n (mm_err_puts).  The reference asserts an intron of at least 2 bases and a
+// walk that ends at re: a CIGAR that breaks either is refused before a byte is written.
+void put_junc(Text &o, const FlatIndex &fi, const Bseq1 &t, const Reg1 &r)
+{
+	junc_hit_check(fi, t, r);
+	int64_t end = r.rs;
+	bool bad = false;
+	for (uint32_t i = 0; i < r.p->n_cigar; ++i) {
+		const uint32_t op = r.p->cigar[i] & 0xf, len = r.p->cigar[i] >> 4;
+		bad |= op > 9 || (op == 3 && len < 2);
+		if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) end += len;
+	}
+	if (bad || end != r.re) throw std::invalid_argument(kJuncBadCigar);
+	const bool rev = (r.p->trans_strand == 2) != (r.rev != 0);
+	const std::string &tname = fi.names[r.rid];
+	uint32_t t_off = (uint32_t)r.rs;
+	for (uint32_t i = 0; i < r.p->n_cigar; ++i) {
+		const uint32_t op = r.p->cigar[i] & 0xf, len = r.p->cigar[i] >> 4;
+		if (op == 0 || op == 2 || op == 7 || op == 8) t_off += len;
+		if (op != 3) continue;
+		uint8_t donor[2], acceptor[2];
+		if (!rev) fi.getseq(r.rid, t_off, t_off + 2, donor), fi.getseq(r.rid, t_off + len - 2, t_off + len, acceptor);
+		else { // revcomp_splice (format.c:256-261) of the two ends, swapped
+			uint8_t a[2], d[2];
+			fi.getseq(r.rid, t_off, t_off + 2, a), fi.getseq(r.rid, t_off + len - 2, t_off + len, d);
+			donor[0] = d[1] < 4 ? 3 - d[1] : 4, donor[1] = d[0] < 4 ? 3 - d[0] : 4;
+			acceptor[0] = a[1] < 4 ? 3 - a[1] : 4, acceptor[1] = a[0] < 4 ? 3 - a[0] : 4;
+		}
+		const int score1 = donor[0] == 2 && donor[1] == 3 ? 3 : donor[0] == 2 && donor[1] == 1 ? 2 : donor[0] == 0 && donor[1] == 3 ? 1 : 0;
+		const int score2 = acceptor[0] == 0 && acceptor[1] == 2 ? 3 : acceptor[0] == 0 && acceptor[1] == 1 ? 1 : 0;
+		o.str(tname.data(), tname.size()), o.ch('\t'), o.num(t_off), o.ch('\t'), o.num(t_off + len), o.ch('\t'), o.str(t.name), o.ch('\t'), o.num(score1 + score2), o.ch('\t'),
+			o.ch("+-"[rev]), o.ch('\n');
+		t_off += len;
+	}
+}
+
 #if defined(__x86_64__)
 // Reverse complement, 16 bases per step, for blocks made of A/C/G/T/N in either case: the low nibbles of these five letters differ
 // (1, 3, 7, 4, 14), so one byte shuffle maps a letter to its complement and another checks that the block holds nothing else.
@@ -494,7 +551,6 @@ void put_sam(Text &o, const FlatIndex &fi, const Bseq1 &t, int seg_idx, int reg_
 
 std::string format_check(const MapOpt &opt)
 {
-	if (opt.flag & F_OUT_JUNC) return "--write-junc output is not implemented";
 	if (opt.split_prefix) return "split-index output is not implemented";
 	return "";
 }
@@ -523,7 +579,9 @@ static void format_range(const FlatIndex &fi, const MapOpt &opt, const int *seg_
 			const Bseq1 &t = seq[i];
 			const Reg1 *regs = (const Reg1 *)reg[i];
 			const int rl = rep_len ? rep_len[i] : -1;
-			if (n_reg[i] > 0) {
+			if (flag & F_OUT_JUNC) { // --write-junc (map.c:601-607): ahead of the SAM / PAF branches, the other output flags play no part
+				for (int j = 0; j < n_reg[i]; ++j) if (junc_printable(regs[j])) put_junc(o, fi, t, regs[j]);
+			} else if (n_reg[i] > 0) {
 				for (int j = 0; j < n_reg[i]; ++j) {
 					if ((flag & F_NO_PRINT_2ND) && regs[j].id != regs[j].parent) continue;
 					if (flag & F_OUT_SAM) put_sam(o, fi, t, i - seg_st, j, ns, &n_reg[seg_st], &reg[seg_st], flag, rl, sq);
@@ -548,6 +606,7 @@ static size_t format_parts(const FlatIndex &fi, const MapOpt &opt, int n_threads
                            void *const *reg, const int *rep_len, std::vector<Text> &parts, std::vector<size_t> &off)
 {
 	const long chunk = 64, n_chunks = (n + chunk - 1) / chunk;
+	if (opt.flag & F_OUT_JUNC) junc_index_check(fi);
 	if ((long)parts.size() < n_chunks) parts.resize(n_chunks);
 	static const bool trace = getenv("MM2AMD_FMT_TRACE") != nullptr;
 	const auto t0 = std::chrono::steady_clock::now();
@@ -641,6 +700,67 @@ char *hole_into(char *w, const Bseq1 &t, const Reg1 *r, int64_t flag)
 	return w;
 }
 
+// --write-junc on the device (junc_text.hpp): a job and a hit per printable hit, in format_range's order; the kernel's sizing pass judges the CIGARs
+const char *format_junc_dev(Backend &be, const FlatIndex &fi, const MapOpt &opt, int n_threads, long n_frag, const int *seg_off, const int *n_seg, const Bseq1 *seq,
+                            const int *n_reg, void *const *reg, FormatScratch &fs, size_t *out_len)
+{
+	junc_index_check(fi);
+	struct JuncPlan { int read, j; bool first; uint64_t name_off, cig_off; }; // first: the first printable hit of its read copies the name
+	std::vector<JuncPlan> plan;
+	Backend::RecTextSizes sz;
+	for (long f = 0; f < n_frag; ++f) {
+		const int seg_st = seg_off ? seg_off[f] : (int)f, ns = n_seg ? n_seg[f] : 1;
+		for (int i = seg_st; i < seg_st + ns; ++i) {
+			const Reg1 *regs = (const Reg1 *)reg[i];
+			bool first = true;
+			for (int j = 0; j < n_reg[i]; ++j) {
+				if (!junc_printable(regs[j])) continue;
+				junc_hit_check(fi, seq[i], regs[j]);
+				plan.push_back(JuncPlan{ i, j, first, sz.name_bytes, sz.cigar_words });
+				sz.cigar_words += regs[j].p->n_cigar, first = false;
+			}
+			if (!first) sz.name_bytes += strlen(seq[i].name);
+		}
+	}
+	sz.n_jobs = sz.n_hits = plan.size();
+	if (sz.n_jobs > 0x7fffffffull) throw std::invalid_argument("[mm2amd] --write-junc: too many hits in one batch");
+	const Backend::RecTextBufs B = be.rec_text_begin(sz);
+	const long chunk = 256, n_chunks = ((long)sz.n_jobs + chunk - 1) / chunk;
+	parallel_for_side(n_threads, n_chunks, [&](long c, int) {
+		for (size_t k = (size_t)(c * chunk); k < std::min(sz.n_jobs, (size_t)((c + 1) * chunk)); ++k) {
+			const JuncPlan &pl = plan[k];
+			const Bseq1 &t = seq[pl.read];
+			const Reg1 &r = ((const Reg1 *)reg[pl.read])[pl.j];
+			const uint32_t name_len = (uint32_t)strlen(t.name);
+			if (pl.first) memcpy(B.names + pl.name_off, t.name, name_len);
+			RecHit &h = B.hits[k];
+			memset(&h, 0, sizeof h);
+			h.rid = r.rid, h.rs = r.rs, h.re = r.re, h.qs = r.qs, h.qe = r.qe, h.n_cigar = r.p->n_cigar, h.cig_off = pl.cig_off, h.t_pos = fi.seq_off[r.rid];
+			h.bits = r.mapq | (r.rev ? kRecRev : 0u) | kRecHasP | kRecIsParent | kRecIsSpliced | (uint32_t)r.p->trans_strand << kRecTransShift;
+			memcpy(B.cigar + pl.cig_off, r.p->cigar, (size_t)r.p->n_cigar * 4);
+			RecJob &J = B.jobs[k];
+			J.name_off = pl.name_off, J.name_len = name_len, J.l_seq = t.l_seq, J.rep_len = -1, J.hit = (int32_t)k, J.hit0 = (uint32_t)k, J.n_hits = 1;
+		}
+	}, 1);
+	const RecRes *res = be.junc_text_size(opt.flag);
+	uint64_t total = 0;
+	for (size_t k = 0; k < sz.n_jobs; ++k) {
+		if (res[k].status != kRecOk) throw std::invalid_argument(kJuncBadCigar);
+		B.off[k] = total, total += res[k].len;
+	}
+	const char *text = be.junc_text_write(total);
+	if (fs.cap < total + 1) { // grow-only, as format_batch_view
+		free(fs.buf);
+		fs.cap = (total + 1) + (total + 1) / 4;
+		fs.buf = (char *)malloc(fs.cap);
+		if (!fs.buf) { fs.cap = 0; return nullptr; }
+	}
+	if (total) memcpy(fs.buf, text, total);
+	fs.buf[total] = 0;
+	*out_len = total;
+	return fs.buf;
+}
+
 } // namespace
 
 const char *format_batch_dev(Backend &be, const FlatIndex &fi, const MapOpt &opt, int n_threads, long n_frag, const int *seg_off, const int *n_seg, const Bseq1 *seq,
@@ -650,6 +770,10 @@ const char *format_batch_dev(Backend &be, const FlatIndex &fi, const MapOpt &opt
 	const bool sam = (flag & F_OUT_SAM) != 0, per_base = (flag & (F_OUT_CS | F_OUT_MD)) != 0, qstrand = (flag & F_QSTRAND) != 0;
 	auto host = [&]() { *on_device = false; return format_batch_view(fi, opt, n_threads, n_frag, seg_off, n_seg, seq, n_reg, reg, rep_len, fs, out_len); };
 	*on_device = true;
+	if (flag & F_OUT_JUNC) { // junction records do not depend on the mate: fragments of one and of two segments are the device's
+		if (!be.writes_records()) return host();
+		return format_junc_dev(be, fi, opt, n_threads, n_frag, seg_off, n_seg, seq, n_reg, reg, fs, out_len);
+	}
 	if (!be.writes_records() || (flag & F_OUT_DS)) return host();
 	if (per_base && ((fi.flag & ref::I_NO_SEQ) || !fi.S)) return host(); // cs / MD of an index without sequence
 	if (n_seg) for (long f = 0; f < n_frag; ++f) if (n_seg[f] != 1) return host();
@@ -706,7 +830,7 @@ const char *format_batch_dev(Backend &be, const FlatIndex &fi, const MapOpt &opt
 				memset(&h, 0, sizeof h);
 				h.rid = r.rid, h.rs = r.rs, h.re = r.re, h.qs = r.qs, h.qe = r.qe, h.mlen = r.mlen, h.blen = r.blen, h.cnt = r.cnt, h.score = r.score, h.subsc = r.subsc, h.div = r.div;
 				h.bits = r.mapq | (uint32_t)r.split << kRecSplitShift | (r.rev ? kRecRev : 0u) | (r.inv ? kRecInv : 0u) | (r.sam_pri ? kRecSamPri : 0u) | (r.p ? kRecHasP : 0u) |
-				         (r.id == r.parent ? kRecIsParent : 0u);
+				         (r.id == r.parent ? kRecIsParent : 0u) | (r.is_spliced ? kRecIsSpliced : 0u);
 				if (r.p) h.dp_max0 = r.p->dp_max0, h.dp_score = r.p->dp_score, h.n_ambi = r.p->n_ambi, h.bits |= (uint32_t)r.p->trans_strand << kRecTransShift;
 				const bool printed = job < job_end && recs[job].j == j;
 				if (!printed) continue;

@@ -9,6 +9,7 @@
 namespace mm2amd {
 
 constexpr uint32_t kRecRev = 1u << 10, kRecInv = 1u << 11, kRecSamPri = 1u << 12, kRecHasP = 1u << 13, kRecIsParent = 1u << 14; // RecHit::bits; mapq in bits 0-7,
+constexpr uint32_t kRecIsSpliced = 1u << 15;                                                                                      // (mm_reg1_t::is_spliced: junc_text.hpp)
 constexpr int kRecSplitShift = 8, kRecTransShift = 16;                                                                            // split in 8-9, trans_strand in 16-17
 
 struct RecHit { // one per hit of the batch; the hits of a read are neighbours (SA:Z: walks them)

@@ -24,6 +24,7 @@
 #include "aln_text_dev.hpp" // aln_text_kernel (the alignment's text: CIGAR string, cs, MD) is compiled with this translation unit
 #include "ksw_ll_dev.hpp"   // ksw_ll_kernel (the local score with end coordinates of ksw_ll_i16) as well
 #include "rec_text_dev.hpp"  // and rec_text_kernel (whole PAF / SAM records)
+#include "junc_text_dev.hpp" // and junc_text_kernel (--write-junc: the splice junctions of a hit)
 #include "cigar_eqx_dev.hpp" // and cigar_eqx_kernel (MM_F_EQX: the finished CIGAR's matches cut into = and X)
 
 namespace mm2amd {
