@@ -176,6 +176,48 @@ int mm2amd_sdust_limits(int *narrow_cap, int *wide_cap, int *max_len);
 int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, int n_threads, mm2amd_sdust_res_t *res, uint64_t *pool, size_t pool_cap,
                             double *core_seconds);
 
+/* FASTA / FASTQ text into sequence records: kseq_read (kseq.h:192-232, with ks_getuntil2's CR rule, kseq.h:101-149) + kseq2bseq (bseq.c:65-78:
+ * U -> T, u -> t; qual and comment only on request and when not empty) over a buffer in memory -- fastx_lines_kernel, fastx_classify_kernel and
+ * fastx_copy_kernel for the two regular shapes, the host's parser (fastx.hpp) for everything else.  The batching of mm_bseq_read3 (bseq.c:80-119)
+ * and mm_bseq_read_frag2 (bseq.c:131-159) is the caller's (minimap2_amd.FastxReader), as is decompression.
+ * text[0, len) is a block of the file; is_final says that the file ends with it.  The call returns the records that are COMPLETE and *consumed, the
+ * offset of the first byte that belongs to none of them: the caller puts text[consumed, len) in front of the next block.  In a non-final block a
+ * FASTA-type record is complete once the first byte of the next header has been seen, a FASTQ-type record once its quality has reached the
+ * sequence's length on a line that '\n' ends; a final block's end completes what the reference returns at EOF.  A non-final block without a
+ * complete record returns 0 with *n_recs = 0 and *consumed = 0: supply a longer one.
+ * Record i is recs[i]: offsets into pool of its NUL-terminated strings, UINT64_MAX for a string that is absent (NULL in mm_bseq1_t): qual unless
+ * MM2AMD_FASTX_WITH_QUAL is set and the quality is not empty, comment unless MM2AMD_FASTX_WITH_COMMENT is set and the comment is not empty.
+ * An entry with reserved == 1 (l_seq == -2, no strings) stands for a malformed record -- kseq_read's -2: a quality of another length than the
+ * sequence, or a '+' line the file ends in -- after which mm_bseq_read3 ends its batch; only the host class reports such entries.
+ * *path is a function of the buffer alone:
+ *   MM2AMD_FASTX_PATH_FASTQ4  the first byte is '@' and every record is four lines: '@' header, a sequence line of at least one payload byte
+ *                             that begins with none of '>', '+', '@', CR, a '+' line, a quality line of the same payload length; LF or CRLF; the
+ *                             last '\n' may be missing in a final block; the lines of a trailing incomplete record of a non-final block are left;
+ *   MM2AMD_FASTX_PATH_FASTA   the first byte is '>' and no line begins with '+' or '@'; any number of sequence lines, empty lines anywhere,
+ *                             LF or CRLF.  A line that is a lone CR, or a final block that ends in a lone '>', sends the buffer to the host;
+ *   MM2AMD_FASTX_PATH_HOST    everything else: the host's parser on the same buffer (one scan on the device is then lost).
+ * recs == NULL or pool == NULL sizes the call: *n_recs, *pool_len, *consumed and *path are filled.  A capacity that is too small gives
+ * MM2AMD_ENOMEM with the sizes filled; nothing is written at or beyond either capacity.  len == 0 returns 0 with no records.  MM2AMD_EINVAL for a
+ * null text with len > 0, a null out-pointer or len > max_text (2^30); MM2AMD_ENODEV without a device.  Device and pinned buffers are kept
+ * between calls; the call has a stream and a profiler slot of its own and runs one at a time.  MM2AMD_FASTX_LONG_LINE=<n> (read at every call,
+ * at least 16) replaces the payload length from which fastx_copy_kernel's long class copies a line (4096; tests send 100-byte lines through it).
+ * mm2amd_fastx_parse_host is the host's parser alone with the same results (path = HOST): it needs no device and has no length limit.
+ * mm2amd_fastx_limits reports max_text and long_line as in force; either pointer may be NULL.  mm2amd_fastx_last_times is a benchmark hook: the
+ * last mm2amd_fastx_parse's seconds in upload, device work up to the sizes, copy kernels, download, the host's table, the host's parser. */
+#define MM2AMD_FASTX_WITH_QUAL    1
+#define MM2AMD_FASTX_WITH_COMMENT 2
+#define MM2AMD_FASTX_PATH_HOST   0
+#define MM2AMD_FASTX_PATH_FASTQ4 1
+#define MM2AMD_FASTX_PATH_FASTA  2
+typedef struct { uint64_t name, comment, seq, qual;   /* offsets into pool; UINT64_MAX = absent (NULL in mm_bseq1_t) */
+                 uint32_t name_len, comment_len; int32_t l_seq, reserved; } mm2amd_fastx_rec_t;
+int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm2amd_fastx_rec_t *recs, size_t recs_cap, char *pool, size_t pool_cap,
+                       size_t *n_recs, size_t *pool_len, size_t *consumed, int *path);
+int mm2amd_fastx_parse_host(const char *text, size_t len, int is_final, int flags, mm2amd_fastx_rec_t *recs, size_t recs_cap, char *pool, size_t pool_cap,
+                            size_t *n_recs, size_t *pool_len, size_t *consumed, int *path);
+int mm2amd_fastx_limits(size_t *max_text, int *long_line);
+int mm2amd_fastx_last_times(double *out, int cap);
+
 /* The two device-wide primitives of the index build (device_sort.hip), exposed for testing.  mm2amd_sort_pairs_u64: n (key, value) pairs
  * sorted in place by key bits [0, bits), stably -- what radix_sort_128x (ksort.h:101-151, instantiated at sketch.c:13 and called per bucket
  * at index.c:236) yields for pairs whose input order is ascending in the value: rs_hist / rs_chunk_scan / rs_block_offsets / rs_scatter

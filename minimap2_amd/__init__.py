@@ -58,6 +58,11 @@ class SdustRes(C.Structure):  # mm2amd_sdust_res_t
     _fields_ = [("off", C.c_uint64), ("n", C.c_uint32), ("path", C.c_int32)]
 
 
+class FastxRec(C.Structure):  # mm2amd_fastx_rec_t
+    _fields_ = [("name", C.c_uint64), ("comment", C.c_uint64), ("seq", C.c_uint64), ("qual", C.c_uint64), ("name_len", C.c_uint32),
+                ("comment_len", C.c_uint32), ("l_seq", C.c_int32), ("reserved", C.c_int32)]
+
+
 class KswRes(C.Structure):  # mm2amd_ksw_res_t
     _fields_ = [(n, C.c_int32) for n in ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score",
                                          "n_cigar", "reach_end")] + [("cigar_off", C.c_uint32)]
@@ -126,6 +131,9 @@ FMT_PATH_DEVICE, FMT_PATH_HOST = 0, 1  # MM2AMD_FMT_PATH_*: who wrote the text o
 LL_QREV, LL_QCOMP, LL_TREV = 1, 2, 4  # MM2AMD_LL_*
 LL_PATH_WAVE, LL_PATH_WG, LL_PATH_HOST = 0, 1, 2  # MM2AMD_LL_PATH_*
 SDUST_PATH_NARROW, SDUST_PATH_WIDE = 0, 1  # MM2AMD_SDUST_PATH_*
+FASTX_WITH_QUAL, FASTX_WITH_COMMENT = 1, 2  # MM2AMD_FASTX_WITH_*
+FASTX_PATH_HOST, FASTX_PATH_FASTQ4, FASTX_PATH_FASTA = 0, 1, 2  # MM2AMD_FASTX_PATH_*
+F_COPY_COMMENT, F_FRAG_MODE = 0x2000000, 0x2000  # MM_F_COPY_COMMENT, MM_F_FRAG_MODE (minimap.h:35, :23)
 
 _lib = None
 
@@ -175,6 +183,12 @@ def _bind(L):
             L.mm2amd_sdust_batch.argtypes = [C.c_int, C.POINTER(SdustJob), C.c_int, C.POINTER(SdustRes), vp, C.c_size_t]
             L.mm2amd_sdust_limits.argtypes = [ip, ip, ip]
             L.mm2amd_sdust_host_batch.argtypes = [C.c_int, C.POINTER(SdustJob), C.c_int, C.c_int, C.POINTER(SdustRes), vp, C.c_size_t, C.POINTER(C.c_double)]
+        if hasattr(L, "mm2amd_fastx_parse"):
+            szp = C.POINTER(C.c_size_t)
+            L.mm2amd_fastx_parse.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, szp, szp, szp, ip]
+            L.mm2amd_fastx_parse_host.argtypes = L.mm2amd_fastx_parse.argtypes
+            L.mm2amd_fastx_limits.argtypes = [szp, ip]
+            L.mm2amd_fastx_last_times.argtypes = [C.POINTER(C.c_double), C.c_int]
         L.mm2amd_sort_pairs_u64.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mm2amd_exclusive_sum_u32.argtypes = [vp, vp, C.c_uint64]
         L.mm2amd_encode_batch.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
@@ -319,6 +333,257 @@ def read_fastx(fn):
     if not seqs:
         raise Mm2AmdError("%s: no sequence" % fn)
     return names, seqs
+
+
+def _fastx_call(data, is_final, flags, device, L=None):
+    """mm2amd_fastx_parse (device) / mm2amd_fastx_parse_host over a bytes-like `data`: (table, pool, consumed, path) -- the table a numpy
+    record array with the fields of mm2amd_fastx_rec_t, entries with reserved != 0 included, the pool a numpy uint8 array"""
+    import numpy as np
+    L = L or lib()
+    text = np.frombuffer(data, dtype=np.uint8)
+    call = L.mm2amd_fastx_parse if device else L.mm2amd_fastx_parse_host
+    n, pl, used, path = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    rec_cap, pool_cap = text.size // 64 + 16, text.size + 16  # a guess that holds for reads of 30 bases and more; the sizes come back otherwise
+    while True:
+        recs, pool = np.empty(rec_cap, dtype=_fastx_dtype()), np.empty(pool_cap, dtype=np.uint8)
+        rc = call(text.ctypes.data if text.size else None, text.size, 1 if is_final else 0, flags, recs.ctypes.data, rec_cap, pool.ctypes.data, pool_cap,
+                  C.byref(n), C.byref(pl), C.byref(used), C.byref(path))
+        if rc == ENOMEM and (n.value > rec_cap or pl.value > pool_cap):
+            rec_cap, pool_cap = max(rec_cap, n.value), max(pool_cap, pl.value)
+            continue
+        _check(rc, L)
+        return recs[:n.value], pool[:pl.value], used.value, path.value
+
+
+def _fastx_dtype():
+    import numpy as np
+    return np.dtype([("name", "<u8"), ("comment", "<u8"), ("seq", "<u8"), ("qual", "<u8"), ("name_len", "<u4"), ("comment_len", "<u4"), ("l_seq", "<i4"),
+                     ("reserved", "<i4")])
+
+
+def parse_fastx(data, is_final=True, with_qual=True, with_comment=False, device=True):
+    """The complete records of a block of FASTA / FASTQ text, as kseq_read + kseq2bseq return them (mm2amd_fastx_parse; device=False: the host's
+    parser, mm2amd_fastx_parse_host).  Returns (records, consumed, path): each record (name, comment | None, seq, qual | None) as bytes;
+    consumed, the offset of the first byte that belongs to no complete record (put data[consumed:] in front of the next block); path, who
+    parsed it (FASTX_PATH_FASTQ4 / FASTX_PATH_FASTA: the kernels; FASTX_PATH_HOST: the host).  Malformed records are left out."""
+    flags = (FASTX_WITH_QUAL if with_qual else 0) | (FASTX_WITH_COMMENT if with_comment else 0)
+    recs, pool, used, path = _fastx_call(data, is_final, flags, device)
+    raw, none, out = pool.tobytes(), 0xffffffffffffffff, []
+    for r in recs.tolist():
+        if r[7]:
+            continue
+        out.append((raw[r[0]:r[0] + r[4]], None if r[1] == none else raw[r[1]:r[1] + r[5]], raw[r[2]:r[2] + r[6]],
+                    None if r[3] == none else raw[r[3]:r[3] + r[6]]))
+    return out, used, path
+
+
+def fastx_limits():
+    """mm2amd_fastx_limits: max_text, the longest block the device path takes, and long_line as in force"""
+    a, b = C.c_size_t(0), C.c_int(0)
+    _check(lib().mm2amd_fastx_limits(C.byref(a), C.byref(b)))
+    return {"max_text": a.value, "long_line": b.value}
+
+
+def _qname_len(s):  # mm_qname_len (bseq.h:31-36)
+    n = len(s)
+    return n - 2 if n >= 3 and 48 <= s[n - 1] <= 57 and s[n - 2] == 47 else n
+
+
+def _qname_same(a, b):  # mm_qname_same (bseq.h:38-44)
+    la, lb = _qname_len(a), _qname_len(b)
+    return la == lb and a[:la] == b[:lb]
+
+
+class _FastxSource(object):
+    """One sequence file as a stream of parsed blocks: text is read block_bytes at a time behind the unconsumed tail of the block before; a
+    block without a complete record is read again with twice the room."""
+
+    def __init__(self, fn, flags, block_bytes, device):
+        import gzip
+        with open(fn, "rb") as f:
+            gz = f.read(2) == b"\x1f\x8b"
+        self.f = gzip.open(fn, "rb") if gz else open(fn, "rb")  # (decompression stays on the host: the library links no zlib)
+        self.flags, self.block, self.device = flags, max(int(block_bytes), 16), device
+        self.tail, self.done = b"", False
+        self.recs, self.pool, self.i = None, None, 0
+        self.paths = []  # who parsed each block (FASTX_PATH_*)
+
+    def close(self):
+        self.f.close()
+
+    def fill(self):
+        """make self.recs[self.i] the next table entry; False at the end of the file"""
+        while self.recs is None or self.i >= len(self.recs):
+            if self.done:
+                return False
+            want = self.block
+            while True:
+                data = self.f.read(want)
+                final = len(data) < want
+                text = memoryview(self.tail + data if self.tail else data)
+                if self.device and len(text) > fastx_limits()["max_text"]:
+                    raise Mm2AmdError("a single record outgrows the longest block the device reader takes; read the file with device=False")
+                recs, pool, used, path = _fastx_call(text, final, self.flags, self.device)
+                self.paths.append(path)
+                if final or len(recs):
+                    break
+                self.tail, want = bytes(text), max(want, len(text))  # no complete record: the same text and as much again
+            self.tail = b"" if final else bytes(text[used:])
+            self.done = final
+            self.recs, self.pool, self.i = recs, pool, 0
+            self.bad = recs["reserved"] != 0
+            self.l_seq = recs["l_seq"].astype("int64")
+        return True
+
+    def name(self, i):
+        r = self.recs[i]
+        return self.pool[int(r["name"]):int(r["name"]) + int(r["name_len"])].tobytes()
+
+    def run(self):
+        """how many entries from self.i on are good ones"""
+        import numpy as np
+        b = np.flatnonzero(self.bad[self.i:])
+        return int(b[0]) if len(b) else len(self.recs) - self.i
+
+
+class FastxReader(object):
+    """The batches mm_bseq_read3 (bseq.c:80-119) -- or, for a list of two or more files, mm_bseq_read_frag2 (bseq.c:131-159) -- returns for
+    successive calls with chunk_size = chunk_bases, as Batch objects with the fragment table of map.c:560-575; iteration ends, like the
+    reference's pipeline, with the first call that returns no record.  Plain or gzip files.  The records come from mm2amd_fastx_parse (device=True:
+    fastx_lines_kernel / fastx_classify_kernel / fastx_copy_kernel, the host's parser for text that is neither plain FASTA nor four-line FASTQ)
+    or from the host's parser alone (device=False); the batches are the same.
+    with_qual / with_comment: keep the qualities / the comments (kseq2bseq).  frag_mode: MM_F_FRAG_MODE -- a pair is not split across batches and
+    reads of one name form a fragment.  The text is read block_bytes at a time.  paths lists who parsed each block."""
+
+    def __init__(self, fn_or_list, chunk_bases=500_000_000, with_qual=True, with_comment=False, frag_mode=False, block_bytes=64 << 20, device=True):
+        fns = [fn_or_list] if isinstance(fn_or_list, (str, bytes, os.PathLike)) else list(fn_or_list)
+        if not fns:
+            raise Mm2AmdError("FastxReader needs a file")
+        flags = (FASTX_WITH_QUAL if with_qual else 0) | (FASTX_WITH_COMMENT if with_comment else 0)
+        self.src = [_FastxSource(fn, flags, block_bytes, device) for fn in fns]
+        self.chunk_bases, self.frag_mode = int(chunk_bases), bool(frag_mode) or len(fns) > 1
+        self.n_processed = 0
+        self._stash = None  # (source chunk, index) of the read mm_bseq_read3 keeps for its next call
+
+    @property
+    def paths(self):
+        return [p for s in self.src for p in s.paths]
+
+    def close(self):
+        for s in self.src:
+            s.close()
+
+    def __iter__(self):
+        try:
+            while True:
+                parts = self._read_frag2() if len(self.src) > 1 else self._read3()
+                if not parts:
+                    return
+                yield self._batch(parts)
+        finally:
+            self.close()
+
+    # a part: (recs, pool, lo, hi) -- entries lo .. hi - 1 of one parsed block
+    def _read3(self):
+        import numpy as np
+        s, parts, size = self.src[0], [], 0
+        if self._stash is not None:
+            parts.append(self._stash)
+            size = int(self._stash[0][self._stash[2]]["l_seq"])
+            self._stash = None
+        while s.fill():
+            n_good = s.run()
+            if n_good == 0:  # a malformed record: mm_bseq_read3 returns what it has
+                s.i += 1
+                return parts
+            cum = np.cumsum(s.l_seq[s.i:s.i + n_good]) + size
+            k = int(np.searchsorted(cum, self.chunk_bases, side="left"))  # the first record with which the batch holds chunk_bases bases
+            if k >= n_good:
+                parts.append((s.recs, s.pool, s.i, s.i + n_good))
+                size, s.i = int(cum[-1]), s.i + n_good
+                continue
+            parts.append((s.recs, s.pool, s.i, s.i + k + 1))
+            s.i += k + 1
+            if self.frag_mode and int(parts[-1][0][parts[-1][3] - 1]["l_seq"]) < 1000000:  # the rest of the pair (bseq.c:100-109)
+                last = self._name(parts[-1])
+                while s.fill():
+                    if s.bad[s.i]:
+                        s.i += 1
+                        break
+                    one = (s.recs, s.pool, s.i, s.i + 1)
+                    s.i += 1
+                    if not _qname_same(self._name(one), last):
+                        self._stash = one
+                        break
+                    parts.append(one)
+                    last = self._name(one)
+            return parts
+        return parts
+
+    @staticmethod
+    def _name(part):
+        r = part[0][part[3] - 1]
+        return part[1][int(r["name"]):int(r["name"]) + int(r["name_len"])].tobytes()
+
+    def _read_frag2(self):
+        import numpy as np
+        parts, size = [], 0  # a part here: a tuple of one part per file, interleaved record by record
+        while True:
+            have = [s.fill() for s in self.src]
+            k = min(s.run() if h else 0 for s, h in zip(self.src, have))
+            if k == 0:  # a file has ended or holds a malformed record: the round's other records are dropped (bseq.c:140-147)
+                for s, h in zip(self.src, have):
+                    if h:
+                        s.i += 1
+                return parts
+            per_round = sum(s.l_seq[s.i:s.i + k] for s in self.src)
+            cum = np.cumsum(per_round) + size
+            j = int(np.searchsorted(cum, self.chunk_bases, side="left"))
+            take = k if j >= k else j + 1
+            parts.append(tuple((s.recs, s.pool, s.i, s.i + take) for s in self.src))
+            for s in self.src:
+                s.i += take
+            size = int(cum[take - 1])
+            if j < k:
+                return parts
+
+    def _batch(self, parts):
+        import numpy as np
+        dt = np.dtype([("l_seq", "<i4"), ("rid", "<i4"), ("name", "<u8"), ("seq", "<u8"), ("qual", "<u8"), ("comment", "<u8")])
+        none = np.uint64(0xffffffffffffffff)
+
+        def records(part):
+            recs, pool, lo, hi = part
+            r, base = recs[lo:hi], np.uint64(pool.ctypes.data)
+            a = np.zeros(hi - lo, dtype=dt)
+            a["l_seq"], a["name"], a["seq"] = r["l_seq"], r["name"] + base, r["seq"] + base
+            a["qual"] = np.where(r["qual"] == none, np.uint64(0), r["qual"] + base)
+            a["comment"] = np.where(r["comment"] == none, np.uint64(0), r["comment"] + base)
+            return a
+        chunks, keep = [], []
+        for p in parts:
+            if isinstance(p[0], tuple):  # one part per file: record k of every file, then record k + 1
+                cols = [records(q) for q in p]
+                a = np.empty((len(cols[0]), len(cols)), dtype=dt)
+                for c, col in enumerate(cols):
+                    a[:, c] = col
+                chunks.append(a.reshape(-1))
+                keep.extend(q[1] for q in p)
+            else:
+                chunks.append(records(p))
+                keep.append(p[1])
+        arr = np.concatenate(chunks) if len(chunks) > 1 else chunks[0]
+        n = len(arr)
+        arr["rid"] = np.arange(self.n_processed, self.n_processed + n, dtype=np.int64).astype(np.int32)  # (map.c:555-556)
+        self.n_processed += n
+        if self.frag_mode:  # reads of one name, next to each other, are one fragment (map.c:566-571)
+            names = [C.string_at(int(a)) for a in arr["name"]]
+            starts = [0] + [i for i in range(1, n) if not _qname_same(names[i - 1], names[i])]
+            seg_off = np.array(starts, dtype=np.int32)
+        else:
+            seg_off = np.arange(n, dtype=np.int32)
+        n_seg = np.diff(np.append(seg_off, np.int32(n))).astype(np.int32)
+        return Batch.from_pool(arr, keep, seg_off, n_seg)
 
 
 def fin_jobs(jobs):
@@ -614,6 +879,26 @@ def _regs_to_alignments(n, regs, names, lens):
     return out
 
 
+class _PoolItems(object):
+    """Batch.items over records that point into a pool: (name, sequence) pairs made on request"""
+
+    def __init__(self, arr, n):
+        self.arr, self.n = arr, n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return [self[i] for i in range(*k.indices(self.n))]
+        if k < 0:
+            k += self.n
+        if not 0 <= k < self.n:
+            raise IndexError(k)
+        r = self.arr[k]
+        return (r.name, C.string_at(r.seq, r.l_seq))
+
+
 class Batch(object):
     """A mini-batch of reads as the reference's reader hands it to the mapping step: an array of mm_bseq1_t records over host buffers
     (bseq.h:14-17) plus the fragment table (seg_off, n_seg; map.c:560-575).  reads: list of (name, sequence), of sequences, or of
@@ -637,6 +922,23 @@ class Batch(object):
             self.arr[k].l_seq, self.arr[k].rid, self.arr[k].name, self.arr[k].seq = len(sb), k, nb, sb
         self.seg_off, self.n_seg = (C.c_int * max(1, self.n))(*seg_off), (C.c_int * max(1, self.n))(*n_seg)
         self.bases = sum(len(sb) for _, sb in self.items)
+
+    @classmethod
+    def from_pool(cls, records, keep, seg_off, n_seg):
+        """A batch over records that already lie in memory as mm_bseq1_t (FastxReader): records a numpy array with the fields of mm_bseq1_t whose
+        name / seq / qual / comment hold addresses inside the buffers of `keep`, which the batch keeps alive; seg_off / n_seg numpy int32 arrays."""
+        import numpy as np
+        b = cls()
+        records, seg_off, n_seg = np.ascontiguousarray(records), np.ascontiguousarray(seg_off, dtype=np.int32), np.ascontiguousarray(n_seg, dtype=np.int32)
+        assert records.dtype.itemsize == C.sizeof(Bseq1)
+        b.n, b._keep, b.records = len(seg_off), (keep, seg_off, n_seg), records
+        m = len(records)
+        b.arr = (Bseq1 * m).from_buffer(records) if m else (Bseq1 * 1)()
+        b.seg_off = (C.c_int * b.n).from_buffer(seg_off) if b.n else (C.c_int * 1)()
+        b.n_seg = (C.c_int * b.n).from_buffer(n_seg) if b.n else (C.c_int * 1)()
+        b.items = _PoolItems(b.arr, m)
+        b.bases = int(records["l_seq"].sum()) if m else 0
+        return b
 
     def rotated(self, k):
         """the same reads starting at fragment k (fragments k.., then 0..k-1): new record and fragment tables over the SAME sequence

@@ -15,6 +15,7 @@
 #include "ksw_ll.hpp"
 #include "sdust.hpp"
 #include "sdust_core.hpp"
+#include "fastx.hpp"
 #include "threads.hpp"
 #include "trace.hpp"
 #include "device_sort.hpp"
@@ -74,6 +75,47 @@ int sdust_check_args(const char *who, int n_jobs, const mm2amd_sdust_job_t *jobs
 	if (n_jobs < 0 || T <= 0 || (n_jobs > 0 && (!jobs || !res))) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (T must be positive)");
 	for (int i = 0; i < n_jobs; ++i)
 		if (jobs[i].len < 0 || jobs[i].len > kSdustMaxLen || (jobs[i].len > 0 && !jobs[i].seq)) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad job (negative or excessive length, or null sequence)");
+	return 0;
+}
+
+struct FastxApiState { // mm2amd_fastx_parse: kept between calls; one call at a time on a stream of its own
+	std::mutex mu;
+	hipStream_t stream = nullptr;
+	DevBuf<uint8_t> d_text, d_pool;
+	DevBuf<uint32_t> d_tile, d_line, d_dst, d_ridx, d_name, d_state;
+	DevBuf<uint2> d_work;
+	DevBuf<FastxDevRec> d_recs;
+	PinBuf<uint32_t> h_word;
+	PinBuf<FastxDevRec> h_recs;
+	double times[6] = { 0, 0, 0, 0, 0, 0 }; // upload, device work up to the sizes, copy kernels, download, the host's table, the host's parser
+};
+FastxApiState &fastx_state() { static FastxApiState *s = new FastxApiState; return *s; } // (never destroyed: the stream belongs to a runtime that may be gone first)
+KernelProfiler &fastx_prof() { return kernel_profiler(kMaxProfLanes - 2, kMaxReplicas - 1); } // (a slot no mapper lane and no record formatter of fewer than 16 replicas uses)
+
+uint32_t fastx_long_line()
+{
+	const char *e = getenv("MM2AMD_FASTX_LONG_LINE");
+	const long v = e && *e ? strtol(e, nullptr, 10) : (long)kFastxLongLine;
+	return (uint32_t)(v < 16 ? 16 : v > (long)kFastxMaxText ? (long)kFastxMaxText : v);
+}
+
+int fastx_check_args(const char *who, const char *text, size_t len, size_t *n_recs, size_t *pool_len, size_t *consumed, int *path, size_t max_len)
+{
+	if (!n_recs || !pool_len || !consumed || !path || (len > 0 && !text) || len > max_len)
+		return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (a null pointer, or a text above the length limit)");
+	*n_recs = 0, *pool_len = 0, *consumed = 0, *path = MM2AMD_FASTX_PATH_HOST;
+	return 0;
+}
+
+// the host's parser behind both entry points
+int fastx_host(const char *who, const char *text, size_t len, int is_final, int flags, mm2amd_fastx_rec_t *recs, size_t recs_cap, char *pool, size_t pool_cap,
+               size_t *n_recs, size_t *pool_len, size_t *consumed)
+{
+	const bool sizing = !recs || !pool;
+	FastxSink out(sizing ? nullptr : recs, recs_cap, sizing ? nullptr : pool, pool_cap);
+	const size_t used = fastx_parse_host(text, len, is_final != 0, flags, out);
+	*n_recs = out.n_recs, *pool_len = out.pool_len, *consumed = !is_final && out.n_recs == 0 ? 0 : used;
+	if (!sizing && (out.n_recs > recs_cap || out.pool_len > pool_cap)) return fail(MM2AMD_ENOMEM, std::string("[mm2amd] ") + who + ": table or pool too small (a call with recs == NULL gives the sizes)");
 	return 0;
 }
 
@@ -680,6 +722,146 @@ int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, i
 		if (!pool || n_out == 0) return 0;
 		if (n_out > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] sdust_host_batch: pool too small (a call with pool == NULL gives the counts)");
 		for (int i = 0; i < n_jobs; ++i) if (!regs[i].empty()) memcpy(pool + res[i].off, regs[i].data(), regs[i].size() * 8);
+		return 0;
+	});
+}
+
+int mm2amd_fastx_limits(size_t *max_text, int *long_line)
+{
+	if (max_text) *max_text = kFastxMaxText;
+	if (long_line) *long_line = (int)fastx_long_line();
+	return 0;
+}
+
+int mm2amd_fastx_last_times(double *out, int cap)
+{
+	FastxApiState &d = fastx_state();
+	std::lock_guard<std::mutex> lk(d.mu);
+	int n = 0;
+	for (; n < cap && n < 6; ++n) out[n] = d.times[n];
+	return n;
+}
+
+int mm2amd_fastx_parse_host(const char *text, size_t len, int is_final, int flags, mm2amd_fastx_rec_t *recs, size_t recs_cap, char *pool, size_t pool_cap,
+                            size_t *n_recs, size_t *pool_len, size_t *consumed, int *path)
+{
+	if (const int rc = fastx_check_args("fastx_parse_host", text, len, n_recs, pool_len, consumed, path, SIZE_MAX)) return rc;
+	if (len == 0) return 0;
+	return guarded([&]() -> int { return fastx_host("fastx_parse_host", text, len, is_final, flags, recs, recs_cap, pool, pool_cap, n_recs, pool_len, consumed); });
+}
+
+int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm2amd_fastx_rec_t *recs, size_t recs_cap, char *pool, size_t pool_cap,
+                       size_t *n_recs, size_t *pool_len, size_t *consumed, int *path)
+{
+	if (const int rc = fastx_check_args("fastx_parse", text, len, n_recs, pool_len, consumed, path, kFastxMaxText)) return rc;
+	return guarded([&]() -> int {
+		DeviceCtx &dc = device_ctx();
+		FastxApiState &d = fastx_state();
+		std::lock_guard<std::mutex> lk(d.mu);
+		{ std::lock_guard<std::mutex> lk2(dc.mu); ensure_device(dc); } // (no device: MM2AMD_ENODEV, also for an empty text's caller who asked for the device)
+		if (len == 0) return 0;
+		HIP_CHECK(hipSetDevice(dc.device_id));
+		if (!d.stream) HIP_CHECK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+		for (double &t : d.times) t = 0;
+		const auto to_host = [&]() -> int {
+			*path = MM2AMD_FASTX_PATH_HOST;
+			const double t0 = Trace::now();
+			const int rc = fastx_host("fastx_parse", text, len, is_final, flags, recs, recs_cap, pool, pool_cap, n_recs, pool_len, consumed);
+			d.times[5] = Trace::now() - t0;
+			return rc;
+		};
+		const bool fin = is_final != 0, fq = text[0] == '@';
+		if (!fq && text[0] != '>') return to_host();
+		if (!fq && fin && text[len - 1] == '>' && (len == 1 || text[len - 2] == '\n')) return to_host(); // a file that ends in a lone marker holds no record there
+		const bool profiling = KernelProfiler::enabled_flag();
+		KernelProfiler &prof = fastx_prof();
+		hipStream_t st = d.stream;
+		double t0 = Trace::now();
+		FastxParams P;
+		memset(&P, 0, sizeof P);
+		const uint32_t mis = (uint32_t)((uintptr_t)text & 15u);
+		P.text = d.d_text.ensure(len + 64) + 16 + mis; // (the buffers come aligned to 256 bytes: the text keeps the caller's alignment modulo 16)
+		P.len = (uint32_t)len, P.flags = (uint32_t)flags, P.cls = fq ? MM2AMD_FASTX_PATH_FASTQ4 : MM2AMD_FASTX_PATH_FASTA, P.long_line = fastx_long_line();
+		P.n_tiles = (uint32_t)((mis + len + kFastxTile - 1) / kFastxTile);
+		P.tile_cnt = d.d_tile.ensure((size_t)P.n_tiles + 1);
+		P.state = d.d_state.ensure(4);
+		uint32_t *const hw = d.h_word.ensure(8);
+		HIP_CHECK(hipMemcpyAsync((void *)P.text, text, len, hipMemcpyHostToDevice, st));
+		HIP_CHECK(hipMemsetAsync(P.state, 0, 16, st));
+		if (profiling) { stream_wait(st); d.times[0] = Trace::now() - t0; t0 = Trace::now(); }
+		// the '\n' of every tile, their running sum, the number of lines
+		prof.begin(st); fastx_lines_launch(P, false, st); prof.end(st, "fastx_lines_kernel[count]", (double)len, (double)len);
+		device_exclusive_sum_u32(P.tile_cnt, P.tile_cnt, P.n_tiles, st);
+		HIP_CHECK(hipMemcpyAsync(hw, P.tile_cnt + P.n_tiles, 4, hipMemcpyDeviceToHost, st));
+		stream_wait(st);
+		prof.collect();
+		if (!profiling) d.times[0] = Trace::now() - t0, t0 = Trace::now(); // (the upload is not timed apart then: it ends within this wait)
+		P.n_nl = hw[0];
+		if (P.n_nl > len) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: the device counted more lines than bytes");
+		const uint32_t n_all = P.n_nl + (text[len - 1] != '\n' ? 1u : 0u);
+		if (fq) {
+			if (fin && (n_all & 3u)) return to_host(); // the file ends inside a record: what the reference makes of the rest is the host's business
+			P.n_lines = fin ? n_all : (P.n_nl & ~3u);
+			if (P.n_lines == 0) { *path = P.cls; return 0; }
+		} else P.n_lines = n_all;
+		P.line_off = d.d_line.ensure((size_t)P.n_nl + 2);
+		P.dst = d.d_dst.ensure((size_t)P.n_lines + 1), P.name_len = d.d_name.ensure(P.n_lines);
+		if (!fq) P.ridx = d.d_ridx.ensure((size_t)P.n_lines + 1);
+		P.work_cap = (uint32_t)(2 * (len / P.long_line) + len / kFastxLongChunk + 4);
+		P.work = d.d_work.ensure(P.work_cap);
+		prof.begin(st); fastx_lines_launch(P, true, st); prof.end(st, "fastx_lines_kernel[write]", (double)len + 4.0 * P.n_nl, (double)len);
+		prof.begin(st); fastx_classify_launch(P, st); prof.end(st, "fastx_classify_kernel", 16.0 * P.n_lines, (double)P.n_lines);
+		device_exclusive_sum_u32(P.dst, P.dst, P.n_lines, st);
+		if (!fq) device_exclusive_sum_u32(P.ridx, P.ridx, P.n_lines, st);
+		HIP_CHECK(hipMemcpyAsync(hw, P.state, 12, hipMemcpyDeviceToHost, st));
+		HIP_CHECK(hipMemcpyAsync(hw + 3, P.dst + P.n_lines, 4, hipMemcpyDeviceToHost, st));
+		if (!fq) HIP_CHECK(hipMemcpyAsync(hw + 4, P.ridx + P.n_lines, 4, hipMemcpyDeviceToHost, st));
+		if (fq && !fin) HIP_CHECK(hipMemcpyAsync(hw + 5, P.line_off + P.n_lines, 4, hipMemcpyDeviceToHost, st));
+		stream_wait(st);
+		prof.collect();
+		if (hw[0]) return to_host(); // the buffer is not what its first byte promised
+		const uint32_t n_work = hw[1], total = hw[3];
+		if (n_work > P.work_cap) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: more long-line work items than the text can hold");
+		size_t used = len;
+		if (fq) {
+			P.n_rec = P.n_lines / 4, P.pool_len = total;
+			if (!fin) used = hw[5];
+		} else if (fin) {
+			P.n_rec = hw[4], P.pool_len = total + 1;
+		} else { // the last header opens the record the buffer does not complete
+			P.n_rec = hw[4] - 1;
+			const uint32_t last = hw[2];
+			if (last >= P.n_lines) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: the device's last header lies outside the line table");
+			HIP_CHECK(hipMemcpyAsync(hw + 6, P.dst + last, 4, hipMemcpyDeviceToHost, st));
+			HIP_CHECK(hipMemcpyAsync(hw + 7, P.line_off + last, 4, hipMemcpyDeviceToHost, st));
+			stream_wait(st);
+			P.pool_len = P.n_rec ? hw[6] + 1 : 0, used = P.n_rec ? hw[7] : 0;
+		}
+		if (used > len || P.pool_len > len + 1 || (size_t)P.n_rec > len) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: sizes from the device exceed the text");
+		d.times[1] = Trace::now() - t0, t0 = Trace::now();
+		*path = P.cls, *n_recs = P.n_rec, *pool_len = P.pool_len, *consumed = used;
+		if (!recs || !pool || P.n_rec == 0) return 0;
+		if (P.n_rec > recs_cap || P.pool_len > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] fastx_parse: table or pool too small (a call with recs == NULL gives the sizes)");
+		P.pool = d.d_pool.ensure((size_t)total + 16), P.recs = d.d_recs.ensure(P.n_rec);
+		FastxDevRec *const hr = d.h_recs.ensure(P.n_rec);
+		prof.begin(st); fastx_copy_launch(P, false, 0, st); prof.end(st, "fastx_copy_kernel[short]", (double)len + (double)P.pool_len, (double)P.n_lines);
+		if (n_work) { prof.begin(st); fastx_copy_launch(P, true, n_work, st); prof.end(st, "fastx_copy_kernel[long]", 0.0, (double)n_work); }
+		if (profiling) { stream_wait(st); d.times[2] = Trace::now() - t0; t0 = Trace::now(); }
+		HIP_CHECK(hipMemcpyAsync(hr, P.recs, (size_t)P.n_rec * sizeof(FastxDevRec), hipMemcpyDeviceToHost, st));
+		HIP_CHECK(hipMemcpyAsync(pool, P.pool, P.pool_len, hipMemcpyDeviceToHost, st));
+		stream_wait(st);
+		prof.collect();
+		d.times[3] = Trace::now() - t0, t0 = Trace::now();
+		const bool with_qual = (flags & MM2AMD_FASTX_WITH_QUAL) != 0;
+		for (uint32_t r = 0; r < P.n_rec; ++r) { // the public table from the kernels' compact one
+			const FastxDevRec &s = hr[r];
+			mm2amd_fastx_rec_t &o = recs[r];
+			const uint32_t l_seq = fq ? s.l_seq : (r + 1 < P.n_rec ? hr[r + 1].name : P.pool_len) - 1u - s.seq;
+			if (s.name >= P.pool_len || s.seq >= P.pool_len || (uint64_t)s.seq + l_seq >= P.pool_len) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: a record from the device lies outside the pool");
+			o.name = s.name, o.name_len = s.name_len, o.comment_len = s.comment_len, o.comment = s.comment_len ? (uint64_t)s.name + s.name_len + 1 : UINT64_MAX;
+			o.seq = s.seq, o.l_seq = (int32_t)l_seq, o.qual = fq && with_qual ? (uint64_t)s.seq + l_seq + 1 : UINT64_MAX, o.reserved = 0;
+		}
+		d.times[4] = Trace::now() - t0;
 		return 0;
 	});
 }

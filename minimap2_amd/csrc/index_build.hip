@@ -22,6 +22,7 @@
 #include "device_sort.hpp"
 #include "device_sort_dev.hpp"
 #include "sketch_dev.hpp"
+#include "fastx_dev.hpp"     // the readers' kernels (fastx_lines_kernel, fastx_classify_kernel, fastx_copy_kernel) as well
 
 namespace mm2amd {
 

@@ -2,7 +2,10 @@
 """The counterpart of `minimap2 -d`: build the index of a FASTA / FASTQ file (plain or gzip) on the device and write it as a .mmi
 (mm2amd_idx_str + mm2amd_idx_dump; the file loads with the unmodified minimap2).
 
-    tools/mm2amd_index.py [-x preset] [-k K] [-w W] [-H] [--no-seq] [-b bucket_bits] [--json] -d out.mmi ref.fa
+    tools/mm2amd_index.py [-x preset] [-k K] [-w W] [-H] [--no-seq] [-b bucket_bits] [--json] [--device-reader] -d out.mmi ref.fa
+
+--device-reader reads the reference through minimap2_amd.FastxReader on the device (fastx_lines_kernel / fastx_classify_kernel / fastx_copy_kernel;
+comments dropped, qualities not kept) instead of the Python loop of read_fastx; the index is the same.
 
 --json prints one line with the phase times (seconds): read and parse, device build, regroup and serialise (HIP events), device-to-host
 copies (HIP events; they run beside the file write), file write, total, and the bytes written.  --load-back loads the written file again
@@ -31,6 +34,7 @@ def main(argv=None):
     ap.add_argument("-d", dest="out", required=True, help="the .mmi to write")
     ap.add_argument("--json", action="store_true", help="print the phase times as one JSON line")
     ap.add_argument("--load-back", action="store_true", help="load the file again and time that")
+    ap.add_argument("--device-reader", action="store_true", help="read the reference with FastxReader(device=True) instead of read_fastx")
     ap.add_argument("ref", help="FASTA / FASTQ, plain or gzip")
     a = ap.parse_args(argv)
     L = mm.lib()
@@ -42,11 +46,22 @@ def main(argv=None):
     hpc = 1 if (a.hpc or io.flag & mm.I_HPC) else 0
     b = a.bucket_bits or io.bucket_bits
     t_start = time.time()
-    names, seqs = mm.read_fastx(a.ref)
+    if a.device_reader:  # the records stay where the reader left them: the index is built from their addresses
+        import numpy as np
+        batches = list(mm.FastxReader(a.ref, with_qual=False, device=True))
+        if not batches:
+            sys.exit("%s: no sequence" % a.ref)
+        recs = np.concatenate([bt.records for bt in batches])
+        n, bases = len(recs), int(recs["l_seq"].sum())
+        seq_arr = (C.c_char_p * n).from_buffer(np.ascontiguousarray(recs["seq"]))
+        name_arr = (C.c_char_p * n).from_buffer(np.ascontiguousarray(recs["name"]))
+    else:
+        names, seqs = mm.read_fastx(a.ref)
+        n, bases = len(seqs), sum(len(s) for s in seqs)
+        seq_arr, name_arr = (C.c_char_p * n)(*seqs), (C.c_char_p * n)(*names)
     t_read = time.time() - t_start
-    n = len(seqs)
     t0 = time.time()
-    h = L.mm2amd_idx_str(w, k, hpc, b, n, (C.c_char_p * n)(*seqs), (C.c_char_p * n)(*names))
+    h = L.mm2amd_idx_str(w, k, hpc, b, n, seq_arr, name_arr)
     if not h:
         sys.exit("index construction failed: " + L.mm2amd_last_error().decode())
     t_build = time.time() - t0
@@ -57,7 +72,7 @@ def main(argv=None):
         st = mm.idx_io_stats()
     finally:
         mm.idx_destroy(h)
-    res = {"tool": "mm2amd_index", "ref": os.path.basename(a.ref), "k": k, "w": w, "hpc": hpc, "bucket_bits": b, "n_seq": n, "bases": sum(len(s) for s in seqs),
+    res = {"tool": "mm2amd_index", "ref": os.path.basename(a.ref), "k": k, "w": w, "hpc": hpc, "bucket_bits": b, "n_seq": n, "bases": bases, "reader": "FastxReader" if a.device_reader else "read_fastx",
            "read_parse_s": round(t_read, 4), "device_build_s": round(t_build, 4), "dump_s": round(t_dump, 4),
            "regroup_s": round(st["regroup_ms"] / 1e3, 5), "serialise_s": round(st["kernel_ms"] / 1e3, 5), "d2h_s": round(st["copy_ms"] / 1e3, 5),
            "file_write_s": round(st["file_ms"] / 1e3, 4), "image_bytes": int(st["image_bytes"]), "file_bytes": int(st["file_bytes"]),
