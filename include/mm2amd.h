@@ -176,6 +176,55 @@ int mm2amd_sdust_limits(int *narrow_cap, int *wide_cap, int *max_len);
 int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, int n_threads, mm2amd_sdust_res_t *res, uint64_t *pool, size_t pool_cap,
                             double *core_seconds);
 
+/* The hit-list rules of a split-index merge (merge_hits, map.c:520-531) for a batch of read segments -- hits_merge_kernel, one wavefront per
+ * segment.  Segment s owns hits[seg_off[s], seg_off[s + 1]): the records of all index parts concatenated in part order, rid already shifted,
+ * dp_max as mm_update_dp_max left it.  Per segment, in the reference's order: subsc, n_sub and dp_max2 start at 0; mm_hit_sort with opt->alt_drop
+ * (dead hits -- cnt == 0 and not an inversion -- go, a list of one hit is left alone, equal keys come in the order of the reference's unstable
+ * radix sort); mm_set_parent; unless MM2AMD_HM_ALL_CHAINS, mm_select_sub and mm_set_sam_pri.  mm_update_dp_max before and mm_set_mapq2 / mm_pair
+ * after stay with the caller (libm and CIGAR walks in double).
+ * out[k] answers hits[k]: pos is the hit's place in its segment's final list, -1 if it was dropped (every other field is then 0); id, parent,
+ * subsc, n_sub and dp_max2 are the record's fields there (dp_max2 is 0 for a hit without alignment); flags holds MM2AMD_HM_SAM_PRI and
+ * MM2AMD_HM_STRAND_RETAINED (with MM2AMD_HM_ALL_CHAINS the two are the input's).  seg[s].n_kept is the length of the final list and seg[s].path
+ * the class that ran the segment:
+ *   MM2AMD_HM_PATH_NARROW  up to narrow_cap (64) hits, the records in 8.5 KB of LDS
+ *   MM2AMD_HM_PATH_WIDE    up to wide_cap (448) hits, 58 KB of LDS
+ *   MM2AMD_HM_PATH_HOST    more hits than that, or more than 64 live hits two of which have equal sort keys (the order among them is then a
+ *                          property of the radix sort's cycle walk, which the host replays): the same rules on the host's pool threads
+ * MM2AMD_EINVAL for a null argument, descending offsets or a segment above max_hits; n_seg == 0 returns 0; MM2AMD_ENODEV without a device.
+ * mm2amd_hits_merge_host_batch is the host twin (test and benchmark hook; no device): the same rules on n_threads threads, path is
+ * MM2AMD_HM_PATH_HOST throughout; with MM2AMD_HM_WAVE_PARENTS it runs the kernel's lane-wise form of mm_set_parent, lane after lane.
+ * *core_seconds, unless NULL, receives the threads' summed time. */
+#define MM2AMD_HM_PATH_NARROW 0
+#define MM2AMD_HM_PATH_WIDE   1
+#define MM2AMD_HM_PATH_HOST   2
+#define MM2AMD_HM_REV 1u              /* mm2amd_hm_hit_t::flags */
+#define MM2AMD_HM_INV 2u
+#define MM2AMD_HM_ALT 4u
+#define MM2AMD_HM_ALIGNED 8u          /* the hit has an mm_extra_t: dp_max is read, dp_max2 is kept */
+#define MM2AMD_HM_SAM_PRI 16u         /* also in mm2amd_hm_out_t::flags */
+#define MM2AMD_HM_STRAND_RETAINED 32u /* also in mm2amd_hm_out_t::flags */
+#define MM2AMD_HM_HARD_MLEVEL 1u      /* mm2amd_hm_opt_t::flags: MM_F_HARD_MLEVEL */
+#define MM2AMD_HM_ALL_CHAINS 2u       /* MM_F_ALL_CHAINS */
+#define MM2AMD_HM_CHECK_STRAND 4u     /* mm_select_sub's check_strand (0 in merge_hits) */
+#define MM2AMD_HM_WAVE_PARENTS 8u     /* host twin only */
+typedef struct { int32_t cnt, rid, score, qs, qe, rs, re, dp_max; uint32_t hash, flags; } mm2amd_hm_hit_t;
+typedef struct { int32_t pos, id, parent, subsc, n_sub, dp_max2; uint32_t flags; int32_t reserved; } mm2amd_hm_out_t;
+typedef struct { int32_t n_kept, path; } mm2amd_hm_seg_t;
+typedef struct {
+	float mask_level; int32_t mask_len;       /* mm_set_parent */
+	float pri_ratio; int32_t best_n;          /* mm_select_sub */
+	float alt_drop;
+	int32_t sub_diff;                         /* 2 a + b */
+	int32_t min_diff;                         /* 2 k */
+	int32_t min_strand_sc;                    /* 0.8 max_gap */
+	uint32_t flags;
+} mm2amd_hm_opt_t;
+int mm2amd_hits_merge_batch(int n_seg, const uint64_t *seg_off, const mm2amd_hm_hit_t *hits, const mm2amd_hm_opt_t *opt, mm2amd_hm_out_t *out,
+                            mm2amd_hm_seg_t *seg);
+int mm2amd_hits_merge_host_batch(int n_seg, const uint64_t *seg_off, const mm2amd_hm_hit_t *hits, const mm2amd_hm_opt_t *opt, int n_threads,
+                                 mm2amd_hm_out_t *out, mm2amd_hm_seg_t *seg, double *core_seconds);
+int mm2amd_hits_merge_limits(int *narrow_cap, int *wide_cap, int *max_hits);
+
 /* FASTA / FASTQ text into sequence records: kseq_read (kseq.h:192-232, with ks_getuntil2's CR rule, kseq.h:101-149) + kseq2bseq (bseq.c:65-78:
  * U -> T, u -> t; qual and comment only on request and when not empty) over a buffer in memory -- fastx_lines_kernel, fastx_classify_kernel and
  * fastx_copy_kernel for the two regular shapes, the host's parser (fastx.hpp) for everything else.  The batching of mm_bseq_read3 (bseq.c:80-119)
@@ -447,6 +496,28 @@ void mm_gpu_destroy(void);
  * can outlive each other (two Python Aligner objects) remember the generation their init produced and tear down only that one. */
 uint64_t mm_gpu_context_generation(void);        /* of the live context; 0: none */
 int mm_gpu_destroy_if(uint64_t generation);      /* 1: it was the live context and is gone now; 0: left alone */
+
+/* Mapping against a multi-part index, minimap2's --split-prefix (splitidx.c, map.c:476-539, :589-600, :693-736).  First pass, once per index
+ * part: map with opt->split_prefix set (the hits' dp_max is then left for the merge to rank, align.c:1114) and hand every mapped batch to a writer;
+ * PREFIX.NNNN.tmp has the reference's layout byte for byte -- k, n_seq, per sequence name length, name and length; per read segment n_reg, rep_len,
+ * frag_gap; per hit the raw mm_reg1_t, with MM_F_CIGAR (read from *opt at every write) followed by capacity and the mm_extra_t block of capacity
+ * words -- except the eight bytes of mm_reg1_t::p, which are zero.  The reference's mm_split_merge reads these files.
+ * Merge pass: mm2amd_split_merge_open does what mm_split_merge_prep does (the files' headers become an index of names and lengths, the rid shift
+ * of every part, k); MM2AMD_EINVAL for MM_F_OUT_CS / _MD / _DS / _JUNC in opt->flag, as the reference refuses cs and MD.  _batch takes the next
+ * mini-batch of reads IN FILE ORDER (seq: mm_bseq1_t records, l_seq is read) and returns per segment a libc block of mm_reg1_t (mm2amd_free_regs),
+ * rep_len (the largest of the parts) and frag_gap (the first part's): the records of all parts in part order, mm_update_dp_max for long reads,
+ * the hit-list rules (on hits_merge_kernel with MM2AMD_DEVICE_MERGE=1, on the host's routines with 0 and by default), mm_set_mapq2, mm_pair for
+ * two-segment fragments.  _format gives the SAM / PAF text of a merged batch in a malloc'd block (the host writer over the names-only index),
+ * _sq the "@SQ" lines of all parts in part order (malloc'd), _close ends the pass and with remove_tmp removes the files. */
+void *mm2amd_split_open(const char *prefix, const mm2amd_index_t *idx, int part_no);
+int mm2amd_split_write(void *w, const void *opt, int n_seq, const int *n_reg, void *const *reg, const int *rep_len, const int *frag_gap);
+int mm2amd_split_close(void *w);
+void *mm2amd_split_merge_open(const char *prefix, int n_parts, const void *opt);
+int mm2amd_split_merge_batch(void *h, int n_frag, const int *seg_off, const int *n_seg, const void *seq, int *n_reg, void **reg, int *rep_len, int *frag_gap);
+int mm2amd_split_merge_format(void *h, int n_frag, const int *seg_off, const int *n_seg, const void *seq, const int *n_reg, void *const *reg, const int *rep_len,
+                              char **out, size_t *out_len);
+int mm2amd_split_merge_sq(void *h, char **out, size_t *out_len);
+int mm2amd_split_merge_close(void *h, int remove_tmp);
 
 const char *mm2amd_backend_name(void);           /* "hip:gfx950" in the product library */
 int mm2amd_format_fraction(double v, char *buf); /* diagnostics: the output stage's "%.4f" (de:f / dv:f tags; no printf: exact integer arithmetic) into buf[>= 16]; returns the length */

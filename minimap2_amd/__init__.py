@@ -58,6 +58,23 @@ class SdustRes(C.Structure):  # mm2amd_sdust_res_t
     _fields_ = [("off", C.c_uint64), ("n", C.c_uint32), ("path", C.c_int32)]
 
 
+class HmHit(C.Structure):  # mm2amd_hm_hit_t
+    _fields_ = [(n, C.c_int32) for n in ("cnt", "rid", "score", "qs", "qe", "rs", "re", "dp_max")] + [("hash", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class HmOut(C.Structure):  # mm2amd_hm_out_t
+    _fields_ = [(n, C.c_int32) for n in ("pos", "id", "parent", "subsc", "n_sub", "dp_max2")] + [("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class HmSeg(C.Structure):  # mm2amd_hm_seg_t
+    _fields_ = [("n_kept", C.c_int32), ("path", C.c_int32)]
+
+
+class HmOpt(C.Structure):  # mm2amd_hm_opt_t
+    _fields_ = [("mask_level", C.c_float), ("mask_len", C.c_int32), ("pri_ratio", C.c_float), ("best_n", C.c_int32), ("alt_drop", C.c_float),
+                ("sub_diff", C.c_int32), ("min_diff", C.c_int32), ("min_strand_sc", C.c_int32), ("flags", C.c_uint32)]
+
+
 class FastxRec(C.Structure):  # mm2amd_fastx_rec_t
     _fields_ = [("name", C.c_uint64), ("comment", C.c_uint64), ("seq", C.c_uint64), ("qual", C.c_uint64), ("name_len", C.c_uint32),
                 ("comment_len", C.c_uint32), ("l_seq", C.c_int32), ("reserved", C.c_int32)]
@@ -131,6 +148,9 @@ FMT_PATH_DEVICE, FMT_PATH_HOST = 0, 1  # MM2AMD_FMT_PATH_*: who wrote the text o
 LL_QREV, LL_QCOMP, LL_TREV = 1, 2, 4  # MM2AMD_LL_*
 LL_PATH_WAVE, LL_PATH_WG, LL_PATH_HOST = 0, 1, 2  # MM2AMD_LL_PATH_*
 SDUST_PATH_NARROW, SDUST_PATH_WIDE = 0, 1  # MM2AMD_SDUST_PATH_*
+HM_PATH_NARROW, HM_PATH_WIDE, HM_PATH_HOST = 0, 1, 2  # MM2AMD_HM_PATH_*
+HM_REV, HM_INV, HM_ALT, HM_ALIGNED, HM_SAM_PRI, HM_STRAND_RETAINED = 1, 2, 4, 8, 16, 32  # MM2AMD_HM_*: flags of a hit (the last two also of a result)
+HM_HARD_MLEVEL, HM_ALL_CHAINS, HM_CHECK_STRAND, HM_WAVE_PARENTS = 1, 2, 4, 8  # MM2AMD_HM_*: flags of the options
 FASTX_WITH_QUAL, FASTX_WITH_COMMENT = 1, 2  # MM2AMD_FASTX_WITH_*
 FASTX_PATH_HOST, FASTX_PATH_FASTQ4, FASTX_PATH_FASTA = 0, 1, 2  # MM2AMD_FASTX_PATH_*
 F_COPY_COMMENT, F_FRAG_MODE = 0x2000000, 0x2000  # MM_F_COPY_COMMENT, MM_F_FRAG_MODE (minimap.h:35, :23)
@@ -183,6 +203,21 @@ def _bind(L):
             L.mm2amd_sdust_batch.argtypes = [C.c_int, C.POINTER(SdustJob), C.c_int, C.POINTER(SdustRes), vp, C.c_size_t]
             L.mm2amd_sdust_limits.argtypes = [ip, ip, ip]
             L.mm2amd_sdust_host_batch.argtypes = [C.c_int, C.POINTER(SdustJob), C.c_int, C.c_int, C.POINTER(SdustRes), vp, C.c_size_t, C.POINTER(C.c_double)]
+        if hasattr(L, "mm2amd_hits_merge_batch"):
+            L.mm2amd_hits_merge_batch.argtypes = [C.c_int, vp, vp, C.POINTER(HmOpt), vp, vp]
+            L.mm2amd_hits_merge_host_batch.argtypes = [C.c_int, vp, vp, C.POINTER(HmOpt), C.c_int, vp, vp, C.POINTER(C.c_double)]
+            L.mm2amd_hits_merge_limits.argtypes = [ip, ip, ip]
+        if hasattr(L, "mm2amd_split_open"):
+            L.mm2amd_split_open.restype = vp
+            L.mm2amd_split_open.argtypes = [C.c_char_p, vp, C.c_int]
+            L.mm2amd_split_write.argtypes = [vp, vp, C.c_int, ip, C.POINTER(vp), ip, ip]
+            L.mm2amd_split_close.argtypes = [vp]
+            L.mm2amd_split_merge_open.restype = vp
+            L.mm2amd_split_merge_open.argtypes = [C.c_char_p, C.c_int, vp]
+            L.mm2amd_split_merge_batch.argtypes = [vp, C.c_int, ip, ip, vp, ip, C.POINTER(vp), ip, ip]
+            L.mm2amd_split_merge_format.argtypes = [vp, C.c_int, ip, ip, vp, ip, C.POINTER(vp), ip, C.POINTER(vp), C.POINTER(C.c_size_t)]
+            L.mm2amd_split_merge_sq.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+            L.mm2amd_split_merge_close.argtypes = [vp, C.c_int]
         if hasattr(L, "mm2amd_fastx_parse"):
             szp = C.POINTER(C.c_size_t)
             L.mm2amd_fastx_parse.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, szp, szp, szp, ip]
@@ -729,6 +764,59 @@ def sdust_limits():
     return {"narrow_cap": a.value, "wide_cap": b.value, "max_len": c.value}
 
 
+HM_HIT_DTYPE = [(n, "<i4") for n in ("cnt", "rid", "score", "qs", "qe", "rs", "re", "dp_max")] + [("hash", "<u4"), ("flags", "<u4")]
+HM_OUT_DTYPE = [(n, "<i4") for n in ("pos", "id", "parent", "subsc", "n_sub", "dp_max2")] + [("flags", "<u4"), ("reserved", "<i4")]
+
+
+def hm_opt(mask_level=0.5, mask_len=0x7fffffff, pri_ratio=0.8, best_n=5, alt_drop=0.15, sub_diff=8, min_diff=30, min_strand_sc=4000, flags=0):
+    """mm2amd_hm_opt_t; the defaults are minimap2's (a = 2, b = 4: sub_diff = 2 a + b; k = 15: min_diff = 2 k; max_gap = 5000)"""
+    return HmOpt(mask_level, mask_len, pri_ratio, best_n, alt_drop, sub_diff, min_diff, min_strand_sc, flags)
+
+
+def _hm_call(call, segs, opt):
+    import numpy as np
+    n = len(segs)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    if n:
+        off[1:] = np.cumsum([len(s) for s in segs], dtype=np.uint64)
+    hits = np.zeros(max(int(off[n]), 1), dtype=HM_HIT_DTYPE)
+    for s, o in zip(segs, off):
+        hits[int(o):int(o) + len(s)] = np.asarray(s, dtype=HM_HIT_DTYPE)
+    out = np.zeros(max(int(off[n]), 1), dtype=HM_OUT_DTYPE)
+    seg = np.zeros((max(n, 1), 2), dtype=np.int32)
+    _check(call(n, off.ctypes.data, hits.ctypes.data, C.byref(opt), out.ctypes.data, seg.ctypes.data))
+    return [out[int(off[i]):int(off[i + 1])].copy() for i in range(n)], [int(x) for x in seg[:n, 0]], [int(x) for x in seg[:n, 1]]
+
+
+def hits_merge_batch(segs, opt=None):
+    """mm2amd_hits_merge_batch: segs a list of per-segment hit lists, each a structured array of HM_HIT_DTYPE (the records of all index parts in
+    part order, rid shifted, dp_max after mm_update_dp_max).  The rules of merge_hits (map.c:520-531) between mm_update_dp_max and mm_set_mapq2 on
+    hits_merge_kernel, one wavefront per segment.  Returns (out, n_kept, path): per segment an HM_OUT_DTYPE array answering its hits one by one
+    (pos -1: dropped), the length of its final list, and the class that ran it (HM_PATH_*)."""
+    L = lib()
+    return _hm_call(lambda n, off, hits, o, out, seg: L.mm2amd_hits_merge_batch(n, off, hits, o, out, seg), segs, opt or hm_opt())
+
+
+def hits_merge_host_batch(segs, opt=None, n_threads=1, wave_parents=False):
+    """mm2amd_hits_merge_host_batch: the same rules on n_threads host threads (path is HM_PATH_HOST throughout); wave_parents=True runs the kernel's
+    lane-wise form of mm_set_parent.  Returns (out, n_kept, path, core_seconds)."""
+    L = lib()
+    o = opt or hm_opt()
+    if wave_parents:
+        o = HmOpt.from_buffer_copy(o)
+        o.flags |= HM_WAVE_PARENTS
+    cs = C.c_double(0)
+    r = _hm_call(lambda n, off, hits, oo, out, seg: L.mm2amd_hits_merge_host_batch(n, off, hits, oo, n_threads, out, seg, C.byref(cs)), segs, o)
+    return r + (cs.value,)
+
+
+def hits_merge_limits():
+    """mm2amd_hits_merge_limits: narrow_cap and wide_cap (hits a segment may have in either launch class), max_hits (of a segment at all)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().mm2amd_hits_merge_limits(C.byref(a), C.byref(b), C.byref(c)))
+    return {"narrow_cap": a.value, "wide_cap": b.value, "max_hits": c.value}
+
+
 def hits_text(idx, hits, reads, what, is_qstrand=False):
     """mm2amd_hits_text_batch: idx an index handle, hits the addresses of mm_reg1_t records, reads each hit's read (bytes).  Returns each
     hit's text, '' for a hit without base-level alignment (mm_gen_cs_ds_or_MD, format.c:364-375)."""
@@ -978,7 +1066,7 @@ class Aligner(object):
     and closing or collecting it leaves the new context alone."""
 
     def __init__(self, seq=None, preset=None, names=None, k=None, w=None, n_threads=0, cigar=True, sam=False, n_gpus=0, device_ids=None,
-                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0, eqx=False, write_junc=False):
+                 fn_idx_in=None, fn_idx_out=None, part=None, extra_flags=0, sdust_thres=0, eqx=False, write_junc=False, split_prefix=None, opt_overrides=None):
         L = lib()
         self._generation, self._idx, self._staged = 0, None, None  # close() must work on a half-built object
         self.last_format_path = None  # FMT_PATH_* of the last format_raw(device=True)
@@ -1003,10 +1091,16 @@ class Aligner(object):
             self.map_opt.flag |= F_OUT_JUNC | F_CIGAR  # minimap2's --write-junc (main.c)
         if sdust_thres:
             self.map_opt.sdust_thres = sdust_thres
+        for name, value in (opt_overrides or {}).items():  # fields of mm_mapopt_t by name, e.g. {"best_n": 20, "pri_ratio": 0.3} for -N 20 -p 0.3
+            setattr(self.map_opt, name, value)
+        if split_prefix is not None:  # minimap2's --split-prefix: the first pass over one part of a multi-part index (map_split)
+            self._split_prefix = os.fsencode(split_prefix)
+            self.map_opt.split_prefix = self._split_prefix
         from_index = fn_idx_in is not None and idx_is_idx(fn_idx_in)
         if from_index:
             # a prebuilt index: its k, w and flag win over the preset's, as in the reference's reader (mm_idx_reader_read, index.c:621-635)
             self._idx, more = idx_load(fn_idx_in, part or 0)
+            self.more_parts = more  # another part follows this one in the file
             if more and part is None:
                 raise Mm2AmdError("%s holds more than one index part: say which with part=" % fn_idx_in)
             st = self.index_stat()
@@ -1287,6 +1381,159 @@ class Aligner(object):
                  "arena_dev_bytes", "arena_pin_bytes", "arena_dev_used", "arena_pin_used", "n_band512", "n_band_rectangle_big",
                  "n_anchors_prune_in", "n_anchors_prune_kept", "n_reads_prune_redo"]  # (the last three: process-wide since start, like the band counters)
         return dict(zip(names, list(v)[:k]))
+
+
+class SplitWriter(object):
+    """The temp file PREFIX.NNNN.tmp of minimap2's --split-prefix for one index part (mm2amd_split_open / _write / _close): what the reference's
+    first pass writes (splitidx.c:8-31, map.c:589-600), for its mm_split_merge or for SplitMerger to read."""
+
+    def __init__(self, prefix, aligner, part_no):
+        self._al, self._h = aligner, None
+        self._h = lib().mm2amd_split_open(os.fsencode(prefix), aligner._idx, part_no)
+        if not self._h:
+            _check(lib().mm2amd_last_error_code())
+
+    def write(self, n_seq, n_reg, reg, rep_len, frag_gap):
+        """the raw results of a mapped batch of n_seq read segments"""
+        _check(lib().mm2amd_split_write(self._h, C.byref(self._al.map_opt), n_seq, n_reg, reg, rep_len, frag_gap))
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, None
+            _check(lib().mm2amd_split_close(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SplitMerger(object):
+    """The merge pass of minimap2's --split-prefix over the temp files of n_parts parts (mm2amd_split_merge_*; mm_split_merge, map.c:693-736).
+    map_opt: the MapOpt of the first pass (after mm_mapopt_update).  MM2AMD_DEVICE_MERGE=1 sends the hit-list rules through hits_merge_kernel."""
+
+    def __init__(self, prefix, n_parts, map_opt):
+        self._h = lib().mm2amd_split_merge_open(os.fsencode(prefix), n_parts, C.byref(map_opt))
+        if not self._h:
+            _check(lib().mm2amd_last_error_code())
+
+    def sq_lines(self):
+        """the @SQ lines of all parts, in part order"""
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().mm2amd_split_merge_sq(self._h, C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            _libc_free(out)
+
+    def merge(self, batch):
+        """the next mini-batch of reads, in file order -> (n_reg, reg, rep_len, frag_gap), to be freed with mm2amd_free_regs"""
+        m = max(1, len(batch.items))
+        n_reg, reg, rep_len, frag_gap = (C.c_int * m)(), (C.c_void_p * m)(), (C.c_int * m)(), (C.c_int * m)()
+        _check(lib().mm2amd_split_merge_batch(self._h, batch.n, batch.seg_off, batch.n_seg, batch.arr, n_reg, reg, rep_len, frag_gap))
+        return n_reg, reg, rep_len, frag_gap
+
+    def format(self, batch, n_reg, reg, rep_len):
+        """SAM / PAF records of a merged batch, as bytes"""
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().mm2amd_split_merge_format(self._h, batch.n, batch.seg_off, batch.n_seg, batch.arr, n_reg, reg, rep_len, C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            _libc_free(out)
+
+    def close(self, remove_tmp=True):
+        if self._h:
+            h, self._h = self._h, None
+            _check(lib().mm2amd_split_merge_close(h, 1 if remove_tmp else 0))
+
+    def __del__(self):
+        try:
+            self.close(False)
+        except Exception:
+            pass
+
+
+def map_split(fn_idx, read_files, split_prefix, out, preset=None, sam=True, batch_bases=500_000_000, idx_batch_size=8_000_000_000, pg_line=None, keep_tmp=False, cs=False, MD=False, ds=False,
+              **aligner_options):
+    """minimap2's --split-prefix: map the reads of read_files (a file name, or a list of two for read pairs) against every part of fn_idx -- a
+    multi-part .mmi, or a FASTA / FASTQ cut into chunks of idx_batch_size bases (minimap2's -I) -- one part at a time, writing the part's temp file and freeing the part; then write
+    the header (with sam=True: @HD, the @SQ lines of all parts, pg_line if given), merge, format and remove the temp files.  out: a file name or
+    a binary file object.  aligner_options go to Aligner (n_threads, extra_flags, ...).  Returns the number of parts."""
+    L = lib()
+    files = [read_files] if isinstance(read_files, (str, bytes)) else list(read_files)
+    flags = aligner_options.pop("extra_flags", 0) | (0x040 if cs else 0) | (0x1000000 if MD else 0) | (0x2000000000 if ds else 0)  # MM_F_OUT_CS / _MD / _DS
+    if flags & (0x040 | 0x1000000 | 0x2000000000 | F_OUT_JUNC) or aligner_options.get("write_junc"):
+        e = Mm2AmdError("mm2amd error %d: --cs, --MD, --ds and --write-junc do not work with --split-prefix" % EINVAL)
+        e.code = EINVAL
+        raise e
+    multi = idx_is_idx(fn_idx)
+    chunks = None if multi else iter(FastxReader(fn_idx, chunk_bases=idx_batch_size, with_qual=False))  # a sequence file: -I-sized chunks, as mm_idx_gen reads them
+    nxt = None if multi else next(chunks, None)
+    n_parts, map_opt = 0, None
+    try:
+        while True:
+            if multi:
+                al = Aligner(fn_idx_in=fn_idx, part=n_parts, preset=preset, sam=sam, extra_flags=flags, split_prefix=split_prefix, **aligner_options)
+            else:
+                if nxt is None:
+                    raise Mm2AmdError("%s holds no sequence" % fn_idx)
+                cur, nxt = nxt, next(chunks, None)
+                al = Aligner(seq=[q for _, q in cur.items], names=[nm.decode() for nm, _ in cur.items], preset=preset, sam=sam, extra_flags=flags, split_prefix=split_prefix,
+                             **aligner_options)
+                del cur
+            try:
+                more = al.more_parts if multi else nxt is not None
+                w = SplitWriter(split_prefix, al, n_parts)
+                try:
+                    rd = FastxReader(files if len(files) > 1 else files[0], chunk_bases=batch_bases, frag_mode=bool(al.map_opt.flag & F_FRAG_MODE))
+                    for b in rd:
+                        al.stage(b)
+                        m = max(1, len(b.items))
+                        n_reg, reg, rep_len, frag_gap = (C.c_int * m)(), (C.c_void_p * m)(), (C.c_int * m)(), (C.c_int * m)()
+                        _check(L.mm_gpu_map_staged(n_reg, reg, rep_len, frag_gap))
+                        try:
+                            w.write(len(b.items), n_reg, reg, rep_len, frag_gap)
+                        finally:
+                            L.mm2amd_free_regs(len(n_reg), n_reg, reg)
+                    rd.close()
+                finally:
+                    w.close()
+                map_opt = MapOpt.from_buffer_copy(al.map_opt)
+            finally:
+                al.close()
+            n_parts += 1
+            if not more:
+                break
+        keep = os.fsencode(split_prefix)
+        map_opt.split_prefix = keep
+        mg = SplitMerger(split_prefix, n_parts, map_opt)
+        f = open(out, "wb") if isinstance(out, (str, bytes)) else out
+        try:
+            if sam:
+                f.write(b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + mg.sq_lines() + (pg_line or b""))
+            rd = FastxReader(files if len(files) > 1 else files[0], chunk_bases=batch_bases, frag_mode=bool(map_opt.flag & F_FRAG_MODE))
+            for b in rd:
+                n_reg, reg, rep_len, _ = mg.merge(b)
+                try:
+                    f.write(mg.format(b, n_reg, reg, rep_len))
+                finally:
+                    L.mm2amd_free_regs(len(n_reg), n_reg, reg)
+            rd.close()
+        finally:
+            if f is not out:
+                f.close()
+            mg.close(remove_tmp=not keep_tmp)
+    except Exception:
+        if not keep_tmp:
+            for j in range(n_parts + 1):
+                try:
+                    os.remove("%s.%.4d.tmp" % (split_prefix, j))
+                except OSError:
+                    pass
+        raise
+    return n_parts
 
 
 def band_counters():

@@ -15,6 +15,9 @@
 #include "ksw_ll.hpp"
 #include "sdust.hpp"
 #include "sdust_core.hpp"
+#include "hits_merge.hpp"
+#include "split_merge.hpp"
+#include "index_handle.hpp"
 #include "fastx.hpp"
 #include "threads.hpp"
 #include "trace.hpp"
@@ -75,6 +78,27 @@ int sdust_check_args(const char *who, int n_jobs, const mm2amd_sdust_job_t *jobs
 	if (n_jobs < 0 || T <= 0 || (n_jobs > 0 && (!jobs || !res))) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (T must be positive)");
 	for (int i = 0; i < n_jobs; ++i)
 		if (jobs[i].len < 0 || jobs[i].len > kSdustMaxLen || (jobs[i].len > 0 && !jobs[i].seq)) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad job (negative or excessive length, or null sequence)");
+	return 0;
+}
+
+struct HitsMergeApiState { // mm2amd_hits_merge_batch: kept between calls
+	DevBuf<mm2amd_hm_hit_t> d_hits;
+	DevBuf<mm2amd_hm_out_t> d_out;
+	DevBuf<mm2amd_hm_seg_t> d_seg;
+	DevBuf<uint64_t> d_off;
+	DevBuf<uint32_t> d_list;
+	PinBuf<uint32_t> h_list;
+};
+HitsMergeApiState &hm_state() { static HitsMergeApiState s; return s; }
+
+int hm_check_args(const char *who, int n_seg, const uint64_t *seg_off, const mm2amd_hm_hit_t *hits, const mm2amd_hm_opt_t *opt, const mm2amd_hm_out_t *out,
+                  const mm2amd_hm_seg_t *seg)
+{
+	if (n_seg < 0 || (n_seg > 0 && (!seg_off || !opt || !seg))) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments");
+	for (int s = 0; s < n_seg; ++s)
+		if (seg_off[s + 1] < seg_off[s] || seg_off[s + 1] - seg_off[s] > (uint64_t)kHmMaxHits)
+			return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad offsets (descending, or a segment above the hit limit)");
+	if (n_seg > 0 && seg_off[n_seg] > seg_off[0] && (!hits || !out)) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": hits without arrays");
 	return 0;
 }
 
@@ -724,6 +748,177 @@ int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, i
 		for (int i = 0; i < n_jobs; ++i) if (!regs[i].empty()) memcpy(pool + res[i].off, regs[i].data(), regs[i].size() * 8);
 		return 0;
 	});
+}
+
+int mm2amd_hits_merge_limits(int *narrow_cap, int *wide_cap, int *max_hits)
+{
+	if (narrow_cap) *narrow_cap = kHmNarrowCap;
+	if (wide_cap) *wide_cap = kHmWideCap;
+	if (max_hits) *max_hits = kHmMaxHits;
+	return 0;
+}
+
+int mm2amd_hits_merge_batch(int n_seg, const uint64_t *seg_off, const mm2amd_hm_hit_t *hits, const mm2amd_hm_opt_t *opt, mm2amd_hm_out_t *out,
+                            mm2amd_hm_seg_t *seg)
+{
+	if (const int rc = hm_check_args("hits_merge_batch", n_seg, seg_off, hits, opt, out, seg)) return rc;
+	if (n_seg == 0) return 0;
+	return guarded([&]() -> int {
+		DeviceCtx &dc = device_ctx();
+		std::lock_guard<std::mutex> lk(dc.mu);
+		ensure_device(dc);
+		HitsMergeApiState &d = hm_state();
+		const size_t n = (size_t)n_seg;
+		const uint64_t first = seg_off[0], total = seg_off[n] - first;
+		// the segments by class: narrow ones from the front of the list, wide ones from its end; the rest is the host's
+		uint32_t *const h_list = d.h_list.ensure(n);
+		size_t n_narrow = 0, n_wide = 0;
+		double narrow_hits = 0, wide_hits = 0;
+		for (size_t s = 0; s < n; ++s) {
+			const uint64_t m = seg_off[s + 1] - seg_off[s];
+			seg[s].n_kept = -1, seg[s].path = MM2AMD_HM_PATH_HOST;
+			if (m <= (uint64_t)kHmNarrowCap) h_list[n_narrow++] = (uint32_t)s, narrow_hits += (double)m;
+			else if (m <= (uint64_t)kHmWideCap) h_list[n - 1 - n_wide++] = (uint32_t)s, wide_hits += (double)m;
+		}
+		if (n_narrow + n_wide > 0) {
+			d.d_hits.ensure(total + 1), d.d_out.ensure(total + 1), d.d_seg.ensure(n), d.d_off.ensure(n + 1), d.d_list.ensure(n);
+			if (total) HIP_CHECK(hipMemcpyAsync(d.d_hits.p, hits + first, total * sizeof(mm2amd_hm_hit_t), hipMemcpyHostToDevice, dc.stream));
+			HIP_CHECK(hipMemcpyAsync(d.d_off.p, seg_off, (n + 1) * 8, hipMemcpyHostToDevice, dc.stream));
+			HIP_CHECK(hipMemcpyAsync(d.d_list.p, h_list, n * 4, hipMemcpyHostToDevice, dc.stream));
+			HIP_CHECK(hipMemcpyAsync(d.d_seg.p, seg, n * sizeof(mm2amd_hm_seg_t), hipMemcpyHostToDevice, dc.stream));
+			HitsMergeParams P;
+			P.hits = d.d_hits.p, P.seg_off = d.d_off.p, P.first = first, P.out = d.d_out.p, P.seg = d.d_seg.p, P.opt = *opt;
+			KernelProfiler &prof = kernel_profiler(0);
+			if (n_narrow) {
+				P.list = d.d_list.p, P.n_list = (int)n_narrow, P.cap = kHmNarrowCap, P.path = MM2AMD_HM_PATH_NARROW;
+				prof.begin(dc.stream);
+				hits_merge_launch(P, dc.stream);
+				prof.end(dc.stream, "hits_merge_kernel[narrow]", 0.0, narrow_hits);
+			}
+			if (n_wide) {
+				P.list = d.d_list.p + (n - n_wide), P.n_list = (int)n_wide, P.cap = kHmWideCap, P.path = MM2AMD_HM_PATH_WIDE;
+				prof.begin(dc.stream);
+				hits_merge_launch(P, dc.stream);
+				prof.end(dc.stream, "hits_merge_kernel[wide]", 0.0, wide_hits);
+			}
+			HIP_CHECK(hipMemcpyAsync(seg, d.d_seg.p, n * sizeof(mm2amd_hm_seg_t), hipMemcpyDeviceToHost, dc.stream));
+			if (total) HIP_CHECK(hipMemcpyAsync(out + first, d.d_out.p, total * sizeof(mm2amd_hm_out_t), hipMemcpyDeviceToHost, dc.stream));
+			HIP_CHECK(hipStreamSynchronize(dc.stream));
+			prof.collect();
+		}
+		// the host class: by size, or because the kernel met equal keys among more than 64 live hits -- the longest lists of the batch, on the pool's threads
+		std::vector<uint32_t> host_list;
+		for (size_t s = 0; s < n; ++s) {
+			if (seg[s].path == MM2AMD_HM_PATH_HOST) { host_list.push_back((uint32_t)s); continue; }
+			if (seg[s].n_kept < 0 || (uint64_t)seg[s].n_kept > seg_off[s + 1] - seg_off[s]) return fail(MM2AMD_EHIP, "[mm2amd] hits_merge_batch: the device kept more hits than the segment has");
+		}
+		parallel_for(effective_cpus(), (long)host_list.size(), [&](long k, int) {
+			const uint32_t s = host_list[(size_t)k];
+			hm_host_segment(hits + seg_off[s], (int)(seg_off[s + 1] - seg_off[s]), *opt, out + seg_off[s], seg + s);
+		}, 1);
+		return 0;
+	});
+}
+
+int mm2amd_hits_merge_host_batch(int n_seg, const uint64_t *seg_off, const mm2amd_hm_hit_t *hits, const mm2amd_hm_opt_t *opt, int n_threads,
+                                 mm2amd_hm_out_t *out, mm2amd_hm_seg_t *seg, double *core_seconds)
+{
+	if (const int rc = hm_check_args("hits_merge_host_batch", n_seg, seg_off, hits, opt, out, seg)) return rc;
+	if (core_seconds) *core_seconds = 0;
+	if (n_seg == 0) return 0;
+	return guarded([&]() -> int {
+		std::vector<double> busy((size_t)std::max(n_threads, 1), 0.0);
+		parallel_for(n_threads, (long)n_seg, [&](long s, int tid) {
+			const double t0 = Trace::now();
+			hm_host_segment(hits + seg_off[s], (int)(seg_off[s + 1] - seg_off[s]), *opt, out + seg_off[s], seg + s);
+			busy[tid] += Trace::now() - t0;
+		}, 16);
+		if (core_seconds) for (double b : busy) *core_seconds += b;
+		return 0;
+	});
+}
+
+void *mm2amd_split_open(const char *prefix, const mm2amd_index_t *idx, int part_no)
+{
+	void *h = nullptr;
+	if (!prefix || !idx || part_no < 0 || part_no > 9999) { fail(MM2AMD_EINVAL, "[mm2amd] split_open: bad arguments"); return nullptr; }
+	guarded([&]() -> int { h = split_open(prefix, index_flat((const IndexHandle *)idx), part_no); return 0; });
+	return h;
+}
+
+int mm2amd_split_write(void *w, const void *opt, int n_seq, const int *n_reg, void *const *reg, const int *rep_len, const int *frag_gap)
+{
+	if (!w || !opt || n_seq < 0 || (n_seq > 0 && (!n_reg || !reg || !rep_len || !frag_gap))) return fail(MM2AMD_EINVAL, "[mm2amd] split_write: bad arguments");
+	return guarded([&]() -> int {
+		SplitWriter &sw = *(SplitWriter *)w;
+		sw.cigar = (((const ref::MapOpt *)opt)->flag & ref::F_CIGAR) != 0;
+		split_write(sw, n_seq, n_reg, reg, rep_len, frag_gap);
+		return 0;
+	});
+}
+
+int mm2amd_split_close(void *w)
+{
+	SplitWriter *sw = (SplitWriter *)w;
+	if (!sw) return 0;
+	const bool ok = !sw->fp || fclose(sw->fp) == 0;
+	sw->fp = nullptr;
+	const std::string fn = sw->fn;
+	delete sw;
+	return ok ? 0 : fail(MM2AMD_EIO, "[mm2amd] split_close: cannot finish " + fn);
+}
+
+void *mm2amd_split_merge_open(const char *prefix, int n_parts, const void *opt)
+{
+	void *h = nullptr;
+	if (!prefix || !opt) { fail(MM2AMD_EINVAL, "[mm2amd] split_merge_open: bad arguments"); return nullptr; }
+	guarded([&]() -> int {
+		SplitMerger *m = split_merge_open(prefix, n_parts, *(const ref::MapOpt *)opt);
+		m->device = split_device_route();
+		h = m;
+		return 0;
+	});
+	return h;
+}
+
+int mm2amd_split_merge_batch(void *h, int n_frag, const int *seg_off, const int *n_seg, const void *seq, int *n_reg, void **reg, int *rep_len, int *frag_gap)
+{
+	if (!h || n_frag < 0 || (n_frag > 0 && (!seq || !n_reg || !reg || !rep_len || !frag_gap))) return fail(MM2AMD_EINVAL, "[mm2amd] split_merge_batch: bad arguments");
+	return guarded([&]() -> int { split_merge_batch(*(SplitMerger *)h, n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq, n_reg, reg, rep_len, frag_gap); return 0; });
+}
+
+int mm2amd_split_merge_format(void *h, int n_frag, const int *seg_off, const int *n_seg, const void *seq, const int *n_reg, void *const *reg, const int *rep_len, char **out,
+                              size_t *out_len)
+{
+	if (!h || !out || !out_len || n_frag < 0 || (n_frag > 0 && (!seq || !n_reg || !reg))) return fail(MM2AMD_EINVAL, "[mm2amd] split_merge_format: bad arguments");
+	return guarded([&]() -> int {
+		SplitMerger &m = *(SplitMerger *)h;
+		*out = format_batch(m.fi, m.opt, effective_cpus(), n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq, n_reg, reg, rep_len, out_len);
+		return *out ? 0 : fail(MM2AMD_ENOMEM, "[mm2amd] split_merge_format: out of memory");
+	});
+}
+
+int mm2amd_split_merge_sq(void *h, char **out, size_t *out_len)
+{
+	if (!h || !out || !out_len) return fail(MM2AMD_EINVAL, "[mm2amd] split_merge_sq: bad arguments");
+	return guarded([&]() -> int {
+		const std::string s = split_sq_lines(*(SplitMerger *)h);
+		if (!(*out = (char *)malloc(s.size() + 1))) return fail(MM2AMD_ENOMEM, "[mm2amd] split_merge_sq: out of memory");
+		memcpy(*out, s.c_str(), s.size() + 1);
+		*out_len = s.size();
+		return 0;
+	});
+}
+
+int mm2amd_split_merge_close(void *h, int remove_tmp)
+{
+	SplitMerger *m = (SplitMerger *)h;
+	if (!m) return 0;
+	const std::string prefix = m->prefix;
+	const int n = (int)m->fp.size();
+	delete m;
+	if (remove_tmp) for (int j = 0; j < n; ++j) remove(split_tmp_name(prefix, j).c_str()); // mm_split_rm_tmp (splitidx.c:74-84)
+	return 0;
 }
 
 int mm2amd_fastx_limits(size_t *max_text, int *long_line)

@@ -124,6 +124,99 @@ MM2_HD inline void hr_mark_parents(ref::Reg1 *r, int n, uint64_t *cov, int32_t *
 	}
 }
 
+// The same rule for a wavefront (hits_merge_kernel, hits_merge_dev.hpp): the primaries so far are spread over the lanes for both inner passes, and
+// only the commit to the owner's record is one lane's.  Written as the lanes' own pieces, so that the kernel (real cross-lane operations between
+// them) and hr_mark_parents_lanes below (the pieces run lane after lane on the host) execute the same code.
+//   pass 1  lane takes primaries lane, lane + n_lanes, ...: hr_wave_clip writes primary j's interval clipped to hit i into cov[j] (HR_NO_COV: they do
+//           not overlap); then hr_wave_cov_part gives, for the lane's own entries, what each adds to the union of all -- its part beyond the furthest
+//           finish among the entries that sort before it by (start, finish, j).  The sum over the lanes is the covered length, and the uncovered
+//           length is the hit's length minus it: the value the reference's sweep over the sorted list ends with (every entry lies inside the hit).
+//   pass 2  hr_wave_owns(primary j, hit i): the reference's test; the owner is the FIRST primary that passes (a ballot per 64 primaries).
+//   commit  hr_wave_commit: what hr_mark_parents does to owner and hit.
+constexpr uint64_t HR_NO_COV = ~0ull;
+MM2_HD inline uint64_t hr_wave_clip(const ref::Reg1 &rp, int si, int ei)
+{
+	int sj = rp.qs, ej = rp.qe;
+	if (ej <= si || sj >= ei) return HR_NO_COV;
+	sj = sj < si ? si : sj, ej = ej > ei ? ei : ej;
+	return (uint64_t)sj << 32 | (uint32_t)ej;
+}
+MM2_HD inline int hr_wave_cov_part(const uint64_t *cov, int n_prim, int lane, int n_lanes, bool *any)
+{
+	int part = 0;
+	for (int j = lane; j < n_prim; j += n_lanes) {
+		const uint64_t v = cov[j];
+		if (v == HR_NO_COV) continue;
+		*any = true;
+		int x = (int)(v >> 32); // the furthest finish before this entry, not below its own start
+		for (int b = 0; b < n_prim; ++b) {
+			const uint64_t u = cov[b];
+			if (u == HR_NO_COV || !(u < v || (u == v && b < j))) continue;
+			x = (int32_t)u > x ? (int32_t)u : x;
+		}
+		if ((int32_t)v > x) part += (int32_t)v - x;
+	}
+	return part;
+}
+MM2_HD inline bool hr_wave_owns(const ref::Reg1 &rp, const ref::Reg1 &ri, int uncov, float mask_level, int mask_len)
+{
+	const int si = ri.qs, ei = ri.qe, len_i = ei - si, sj = rp.qs, ej = rp.qe, len_j = ej - sj;
+	if (ej <= si || sj >= ei) return false;
+	const int mn = len_j < len_i ? len_j : len_i, mx = len_j > len_i ? len_j : len_i, lo = si > sj ? si : sj, hi = ei < ej ? ei : ej;
+	const int ol = hi > lo ? hi - lo : 0;
+	return (float)ol / mn - (float)uncov / mx > mask_level && uncov <= mask_len;
+}
+MM2_HD inline void hr_wave_commit(ref::Reg1 &rp, ref::Reg1 &ri, int sub_diff, float alt_diff_frac)
+{
+	const int len_i = ri.qe - ri.qs, len_j = rp.qe - rp.qs, mn = len_j < len_i ? len_j : len_i;
+	const int lo = ri.qs > rp.qs ? ri.qs : rp.qs, hi = ri.qe < rp.qe ? ri.qe : rp.qe, ol = hi > lo ? hi - lo : 0;
+	const bool handicap = !rp.is_alt && ri.is_alt;
+	int sci = handicap ? hr_alt_score(ri.score, alt_diff_frac) : ri.score;
+	bool counts = ri.cnt >= rp.cnt;
+	ri.parent = rp.parent;
+	rp.subsc = rp.subsc > sci ? rp.subsc : sci;
+	if (rp.p && ri.p && (rp.rid != ri.rid || rp.rs != ri.rs || rp.re != ri.re || ol != mn)) {
+		sci = handicap ? hr_alt_score(ri.p->dp_max, alt_diff_frac) : ri.p->dp_max;
+		rp.p->dp_max2 = rp.p->dp_max2 > sci ? rp.p->dp_max2 : sci;
+		if (rp.p->dp_max - ri.p->dp_max <= sub_diff) counts = true;
+	}
+	if (counts) ++rp.n_sub;
+}
+// the wave-wide form on the host: n_lanes lanes, each piece run for every lane before the next piece starts (a test runs it against hr_mark_parents)
+inline void hr_mark_parents_lanes(ref::Reg1 *r, int n, uint64_t *cov, int32_t *prim, float mask_level, int mask_len, int sub_diff, bool hard_mask_level, float alt_diff_frac, int n_lanes)
+{
+	if (n <= 0) return;
+	for (int i = 0; i < n; ++i) r[i].id = i;
+	int n_prim = 1;
+	prim[0] = 0, r[0].parent = 0;
+	for (int i = 1; i < n; ++i) {
+		const int si = r[i].qs, ei = r[i].qe;
+		int uncov = 0;
+		bool touches = hard_mask_level;
+		if (!hard_mask_level) {
+			for (int lane = 0; lane < n_lanes; ++lane)
+				for (int j = lane; j < n_prim; j += n_lanes) cov[j] = hr_wave_clip(r[prim[j]], si, ei);
+			int covered = 0;
+			bool any = false;
+			for (int lane = 0; lane < n_lanes; ++lane) covered += hr_wave_cov_part(cov, n_prim, lane, n_lanes, &any);
+			if (any) touches = true, uncov = (ei - si) - covered;
+		}
+		int owner = -1;
+		if (touches)
+			for (int j0 = 0; j0 < n_prim && owner < 0; j0 += n_lanes)
+				for (int lane = 0; lane < n_lanes && owner < 0; ++lane) // (the first set bit of the ballot)
+					if (j0 + lane < n_prim && hr_wave_owns(r[prim[j0 + lane]], r[i], uncov, mask_level, mask_len)) owner = j0 + lane;
+		if (owner < 0) prim[n_prim++] = i, r[i].parent = i, r[i].n_sub = 0;
+		else hr_wave_commit(r[prim[owner]], r[i], sub_diff, alt_diff_frac);
+	}
+}
+
+// mm_hit_sort's key of a hit (hit.c:199-203): the alignment's score if it has one, else the chain's, marked down on an ALT contig, with the hash below it
+MM2_HD inline uint64_t hr_sort_key(int score, uint32_t hash, bool is_alt, float alt_diff_frac)
+{
+	return (uint64_t)(is_alt ? hr_alt_score(score, alt_diff_frac) : score) << 32 | hash;
+}
+
 // which hit is reported as the primary SAM record (mm_set_sam_pri, hit.c:220-229); returns the number of primaries
 MM2_HD inline int hr_mark_sam_primary(ref::Reg1 *r, int n)
 {
