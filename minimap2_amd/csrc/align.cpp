@@ -15,12 +15,11 @@
 #include <immintrin.h>
 #endif
 #include "chain_host.hpp"
+#include "tables.hpp"
 
 namespace mm2amd {
 
 using namespace ref;
-
-extern const uint8_t kNt4Table[256];
 
 namespace {
 inline int span_of(const Anchor &a) { return (int)(a.y >> 32 & 0xff); }

@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <thread>
 #include "backend.hpp"
+#include "capi_internal.hpp"
 #include "chain_dump.hpp"
 #include "chain_host.hpp"
 #include "device_ctx.hpp"
@@ -26,10 +27,10 @@
 #include "trace.hpp"
 #include "sdust_core.hpp"
 #include "sdust.hpp"
+#include "stage_run.hpp"
+#include "tables.hpp"
 
 namespace mm2amd {
-
-extern const uint8_t kNt4Table[256];
 
 namespace {
 
@@ -63,8 +64,7 @@ struct Lane {
 	PinBuf<unsigned long long> h_lj_cursor;
 	DevBuf<FinRegion> d_fin_regions; DevBuf<FinPiece> d_fin_pieces; DevBuf<uint32_t> d_fin_out; DevBuf<FinResult> d_fin_res; // region_finish.hip
 	PinBuf<FinRegion> h_fin_regions; PinBuf<FinPiece> h_fin_pieces; PinBuf<uint32_t> h_fin_out; PinBuf<FinResult> h_fin_res;
-	struct EqxBufs { DevBuf<uint32_t> d_n, d_out; DevBuf<uint64_t> d_off; PinBuf<uint32_t> h_n, h_out; PinBuf<uint64_t> h_off; }; // cigar_eqx_dev.hpp: the regions' =/X lengths, their places, the pool
-	EqxBufs eqx_fin, eqx_rg; // of finish_regions / of align_regions: the views align_regions hands out live on while the hand-backs' rounds call finish_regions
+	EqxBufs eqx_fin, eqx_rg; // (stage_run.hpp) of finish_regions / of align_regions: the views align_regions hands out live on while the hand-backs' rounds call finish_regions
 	// align_regions (region_dev.hpp): the lane's last seed_chain() in device terms, the hit / window / piece arrays, the results' host copies
 	long rg_lo = 0; size_t rg_n = 0; uint64_t rg_n_v = 0, rg_n_v2 = 0, rg_n_u = 0, rg_n_u2 = 0;
 	std::vector<int8_t> rg_src; std::vector<uint64_t> rg_aoff, rg_uoff; std::vector<int32_t> rg_nu, rg_nv;
@@ -99,9 +99,7 @@ public:
 	HipBackend(const FlatIndex &fi, DeviceIndexTables *tables, int n_threads, int device, int replica, int tables_device) : T_(tables)
 	{
 		replica_ = replica;
-		DeviceCtx &d = device_ctx(device);
-		std::lock_guard<std::mutex> lk(d.mu);
-		ensure_device(d);
+		DeviceScope scope(device); DeviceCtx &d = scope.dc;
 		dev_ = d.device_id;
 		stream_ = d.stream;
 		n_cu_ = d.n_cu;
@@ -303,23 +301,17 @@ public:
 			B.unit_first = d_unit_first_.p + lo, B.unit_off = d_unit_off_.p, B.unit_cnt = ln.d_mz_cnt.p - ulo, B.mz_cnt = nullptr;
 		// -T: drop minimizers in low-complexity regions (the seed arrays are still unused: they carry the regions).  MM2AMD_DEVICE_SDUST=1: the regions
 		// come from sdust_kernel on the encoded reads, in its two launch classes (sdust.hpp), on this stream; otherwise from the host threads
-		const bool dev_sdust = P.sdust_thres > 0 && env_on("MM2AMD_DEVICE_SDUST"), sdust_no_narrow = env_on("MM2AMD_SDUST_NO_NARROW"); // (read at every call, as mm2amd_sdust_batch reads its two)
+		const bool dev_sdust = P.sdust_thres > 0 && env_on("MM2AMD_DEVICE_SDUST"), sdust_no_narrow = sdust_env_no_narrow();
 		if (dev_sdust) {
 			ln.d_sdust_list.ensure(n_unit), ln.d_sdust_cnt.ensure(1);
 			HIP_CHECK(hipMemsetAsync(ln.d_sdust_cnt.p, 0, sizeof(SdustCounters), st));
 			SdustParams S;
 			S.codes = B.qpool, S.off = Bu.seq_off, S.code_mul = 2, S.n_reads = (int)n_unit, S.T = P.sdust_thres < kSdustMaxT ? P.sdust_thres : kSdustMaxT;
 			S.reg_n = B.sd_n, S.reg_s = B.sd_off, S.reg_e = B.sd_aoff, S.wide_list = ln.d_sdust_list.p, S.cnt = ln.d_sdust_cnt.p;
-			const char *e_cap = getenv("MM2AMD_SDUST_NARROW_CAP");
-			const long cap = e_cap && *e_cap ? strtol(e_cap, nullptr, 10) : kSdustNarrowCap;
-			if (sdust_no_narrow) {
-				S.cap = kSdustWideCap, S.wide = 2;
-				kp.begin(st); sdust_launch(S, 0, st); kp.end(st, "sdust_kernel[wide]", 0.0);
-			} else {
-				S.cap = (int)(cap < 1 ? 1 : cap > kSdustWideCap ? kSdustWideCap : cap), S.wide = 0;
-				kp.begin(st); sdust_launch(S, 0, st); kp.end(st, "sdust_kernel[narrow]", 0.0);
-				S.cap = kSdustWideCap, S.wide = 1; // the reads that stopped: the launch reads the list's length on the device
-				kp.begin(st); sdust_launch(S, 0, st); kp.end(st, "sdust_kernel[wide]", 0.0);
+			if (sdust_no_narrow) sdust_run_class(S, 2, 0, kp, 0.0, st);
+			else {
+				sdust_run_class(S, 0, 0, kp, 0.0, st);
+				sdust_run_class(S, 1, 0, kp, 0.0, st); // the reads that stopped: the launch reads the list's length on the device
 			}
 			HIP_CHECK(hipMemcpyAsync(ln.h_sdust_cnt.ensure(1), ln.d_sdust_cnt.p, sizeof(SdustCounters), hipMemcpyDeviceToHost, st)); // (read after the wait below)
 			kp.begin(st); launch_dust_filter(B, st); kp.end(st, "dust_filter_kernel", 16.0 * est_mz);
@@ -884,15 +876,8 @@ public:
 		const size_t out_words = cur[RGN_CUR_OUT];
 		ln.d_rg_out.ensure(out_words + 1);
 		if (n_regs && cur[RGN_CUR_N_FIN]) {
-			FinParams P;
-			P.regions = ln.d_rg_fin.p, P.n_regions = (int)n_regs, P.pieces = ln.d_rg_pieces.p, P.cigar_pool = d_cigar, P.out_pool = ln.d_rg_out.p, P.results = ln.d_rg_finres.p;
-			P.qpool = R.d_qpool.p, P.S = T_->S.p;
-			memcpy(P.mat, sc.mat, 25);
-			P.q = sc.q, P.e = sc.e, P.log_gap = log_gap ? 1 : 0;
-			P.cap_ops = (int)std::min<uint32_t>((std::max<uint32_t>(cur[RGN_CUR_MAX_OPS], 1u) + 63) & ~63u, (uint32_t)kFinMaxOps);
-			kp.begin(st);
-			region_finish_launch(P, st);
-			kp.end(st, "region_finish_kernel", (double)out_words * 8.0 + (double)cur[RGN_CUR_N_FIN] * (sizeof(FinRegion) + sizeof(FinResult)), (double)cur[RGN_CUR_N_FIN]);
+			finish_run(ln.d_rg_fin.p, (int)n_regs, ln.d_rg_pieces.p, d_cigar, ln.d_rg_out.p, ln.d_rg_finres.p, R.d_qpool.p, T_->S.p, sc.mat, sc.q, sc.e, log_gap, cur[RGN_CUR_MAX_OPS], st, &kp,
+			           (double)out_words * 8.0 + (double)cur[RGN_CUR_N_FIN] * (sizeof(FinRegion) + sizeof(FinResult)), (double)cur[RGN_CUR_N_FIN]);
 			if (O.flag & ref::F_EQX) out.eqx = eqx_pass(ln, ln.eqx_rg, kp, ln.d_rg_fin.p, n_regs, ln.d_rg_finres.p, ln.d_rg_out.p, out_words, R.d_qpool.p);
 		}
 		RgnReadOut *h_rout = ln.h_rg_rout.ensure(n * (size_t)stride);
@@ -931,33 +916,13 @@ public:
 	}
 	// MM_F_EQX (cigar_eqx.hpp) for regions region_finish_kernel has just finished on the lane's stream: count, place (the host waits for the counts: the
 	// pool is sized from their sum), write.  The copy of the pool is queued; the caller waits for the stream.
-	EqxOut eqx_pass(Lane &ln, Lane::EqxBufs &B, KernelProfiler &kp, const FinRegion *d_regions, size_t n, const FinResult *d_res, const uint32_t *d_fin_pool, size_t fin_words, const uint8_t *d_qpool)
+	EqxOut eqx_pass(Lane &ln, EqxBufs &B, KernelProfiler &kp, const FinRegion *d_regions, size_t n, const FinResult *d_res, const uint32_t *d_fin_pool, size_t fin_words, const uint8_t *d_qpool)
 	{
-		hipStream_t st = ln.stream;
 		EqxParams P{};
 		P.regions = d_regions, P.n_regions = (int)n, P.results = d_res, P.fin_pool = d_fin_pool, P.qpool = d_qpool, P.S = T_->S.p;
-		P.n_ops = B.d_n.ensure(n), P.out_off = B.d_off.ensure(n);
-		uint32_t *hn = B.h_n.ensure(n);
-		uint64_t *ho = B.h_off.ensure(n + 1);
-		const double rec_bytes = (double)n * (sizeof(FinRegion) + sizeof(FinResult) + 4);
-		kp.begin(st);
-		cigar_eqx_launch(P, false, st);
-		kp.end(st, "cigar_eqx_kernel[count]", (double)fin_words * 4.0 + rec_bytes, (double)n); // (the sequences' share: eqx_sequence_bytes)
-		HIP_CHECK(hipMemcpyAsync(hn, B.d_n.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		stream_wait(st);
-		uint64_t total = 0;
-		for (size_t i = 0; i < n; ++i) ho[i] = total, total += hn[i];
-		ho[n] = total;
-		HIP_CHECK(hipMemcpyAsync(B.d_off.p, ho, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-		P.out_pool = B.d_out.ensure(total + 1);
-		uint32_t *hout = B.h_out.ensure(total + 1);
-		kp.begin(st);
-		cigar_eqx_launch(P, true, st);
-		kp.end(st, "cigar_eqx_kernel[write]", ((double)fin_words + (double)total) * 4.0 + rec_bytes + (double)n * 8.0, (double)n);
-		if (total) HIP_CHECK(hipMemcpyAsync(hout, B.d_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		EqxOut o;
-		o.n_ops = hn, o.off = ho, o.cigars = hout;
-		return o;
+		const double rec_bytes = (double)n * (sizeof(FinRegion) + sizeof(FinResult) + 4); // (the sequences' share: eqx_sequence_bytes)
+		const uint64_t total = eqx_count(B, P, kp, (double)fin_words * 4.0 + rec_bytes, ln.stream, stream_wait);
+		return eqx_write(B, P, total, kp, ((double)fin_words + (double)total) * 4.0 + rec_bytes + (double)n * 8.0, ln.stream);
 	}
 	// the columns the two passes read, known once the regions' records are on the host: a query byte and half a byte of packed reference per
 	// column, in both passes; a region relabelled in place is not read again by the writing pass
@@ -996,18 +961,11 @@ public:
 		ln.h_fin_out.ensure(out_words + 1), ln.h_fin_res.ensure(n);
 		HIP_CHECK(hipMemcpyAsync(ln.d_fin_regions.p, ln.h_fin_regions.p, n * sizeof(FinRegion), hipMemcpyHostToDevice, ln.stream));
 		HIP_CHECK(hipMemcpyAsync(ln.d_fin_pieces.p, ln.h_fin_pieces.p, pieces.size() * sizeof(FinPiece), hipMemcpyHostToDevice, ln.stream));
-		FinParams P;
-		P.regions = ln.d_fin_regions.p, P.n_regions = (int)n, P.pieces = ln.d_fin_pieces.p, P.cigar_pool = ln.ksw.d_cigar.p, P.out_pool = ln.d_fin_out.p, P.results = ln.d_fin_res.p;
-		P.qpool = res_[ln.set].d_qpool.p, P.S = T_->S.p;
-		memcpy(P.mat, mat25, 25);
-		P.q = (int8_t)q, P.e = (int8_t)e, P.log_gap = log_gap ? 1 : 0;
 		uint32_t longest = 1; // (a region's room in the output pool is the sum of its pieces: the next region's offset minus its own)
 		for (size_t i = 0; i < n; ++i) longest = std::max<uint32_t>(longest, (uint32_t)((i + 1 < n ? regions[i + 1].out_off : (uint32_t)out_words) - regions[i].out_off));
-		P.cap_ops = (int)std::min<uint32_t>((longest + 63) & ~63u, (uint32_t)kFinMaxOps);
 		KernelProfiler &prof = kernel_profiler(lane_id, replica_);
-		prof.begin(ln.stream);
-		region_finish_launch(P, ln.stream);
-		prof.end(ln.stream, "region_finish_kernel", (double)out_words * 8.0 + (double)n * (sizeof(FinRegion) + sizeof(FinResult)), (double)n);
+		finish_run(ln.d_fin_regions.p, (int)n, ln.d_fin_pieces.p, ln.ksw.d_cigar.p, ln.d_fin_out.p, ln.d_fin_res.p, res_[ln.set].d_qpool.p, T_->S.p, mat25, (int8_t)q, (int8_t)e, log_gap, longest,
+		           ln.stream, &prof, (double)out_words * 8.0 + (double)n * (sizeof(FinRegion) + sizeof(FinResult)), (double)n);
 		if (eqx) *eqx = eqx_pass(ln, ln.eqx_fin, prof, ln.d_fin_regions.p, n, ln.d_fin_res.p, ln.d_fin_out.p, out_words, res_[ln.set].d_qpool.p);
 		HIP_CHECK(hipMemcpyAsync(ln.h_fin_res.p, ln.d_fin_res.p, n * sizeof(FinResult), hipMemcpyDeviceToHost, ln.stream));
 		HIP_CHECK(hipMemcpyAsync(ln.h_fin_out.p, ln.d_fin_out.p, out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ln.stream));
@@ -1093,11 +1051,8 @@ private:
 		P.jobs = R.d_jobs.p, P.n_jobs = (int)sz.n_jobs, P.hits = R.d_hits.p, P.flag = flag, P.names = R.d_names.p, P.qpool = R.d_q.p, P.S = T_->S.p, P.cigar = R.d_cigar.p;
 		P.tnames = R.d_tnames.p, P.tname_off = R.d_tname_off.p, P.tlen = R.d_tlen.p, P.res = R.d_res.p, P.off = nullptr, P.out = nullptr;
 		KernelProfiler &prof = kernel_profiler(kMaxProfLanes - 1, replica_);
-		prof.begin(R.stream);
-		if (junc) junc_text_launch(P, false, R.stream); else rec_text_launch(P, false, R.stream);
-		prof.end(R.stream, junc ? "junc_text_kernel[size]" : "rec_text_kernel[size]", (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
-		HIP_CHECK(hipMemcpyAsync(R.h_res.p, R.d_res.p, sz.n_jobs * sizeof(RecRes), hipMemcpyDeviceToHost, R.stream));
-		stream_wait(R.stream);
+		text_size_pass(P, junc ? junc_text_launch : rec_text_launch, R.h_res.p, prof, junc ? "junc_text_kernel[size]" : "rec_text_kernel[size]", (double)sz.cigar_words * 4.0 + (double)sz.q_bytes,
+		          (double)sz.n_jobs, R.stream, stream_wait);
 		prof.collect();
 		return R.h_res.p;
 	}
@@ -1109,14 +1064,9 @@ private:
 		R.h_out.ensure(total + 1);
 		if (sz.n_jobs == 0 || total == 0) return R.h_out.p;
 		R.d_out.ensure(total + 8);
-		HIP_CHECK(hipMemcpyAsync(R.d_off.p, R.h_off.p, sz.n_jobs * 8, hipMemcpyHostToDevice, R.stream));
-		R.P.off = R.d_off.p, R.P.out = R.d_out.p;
 		KernelProfiler &prof = kernel_profiler(kMaxProfLanes - 1, replica_);
-		prof.begin(R.stream);
-		if (junc) junc_text_launch(R.P, true, R.stream); else rec_text_launch(R.P, true, R.stream);
-		prof.end(R.stream, junc ? "junc_text_kernel[write]" : "rec_text_kernel[write]", (double)total + (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs);
-		HIP_CHECK(hipMemcpyAsync(R.h_out.p, R.d_out.p, total, hipMemcpyDeviceToHost, R.stream));
-		stream_wait(R.stream);
+		text_write_pass(R.P, junc ? junc_text_launch : rec_text_launch, R.h_off.p, R.d_off.p, R.d_out.p, R.h_out.p, total, prof, junc ? "junc_text_kernel[write]" : "rec_text_kernel[write]",
+		           (double)total + (double)sz.cigar_words * 4.0 + (double)sz.q_bytes, (double)sz.n_jobs, R.stream, stream_wait);
 		prof.collect();
 		return R.h_out.p;
 	}
@@ -1197,14 +1147,11 @@ Backend *make_backend(const FlatIndex &fi, void *device_tables, int n_threads, i
 {
 	return new HipBackend(fi, (DeviceIndexTables *)device_tables, n_threads, device, replica, tables_device);
 }
-void apply_hw_queue_default(); // capi_common.cpp
 int backend_device_count() { apply_hw_queue_default(); int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
 
 void *backend_build_index_tables(FlatIndex &fi, int device, int *on_device)
 {
-	DeviceCtx &d = device_ctx(device);
-	std::lock_guard<std::mutex> lk(d.mu);
-	ensure_device(d);
+	DeviceScope scope(device); DeviceCtx &d = scope.dc;
 	std::unique_ptr<DeviceIndexTables> T(new DeviceIndexTables);
 	DeviceIndexBuilder::build_from_packed(fi, *T, d.stream);
 	if (on_device) *on_device = d.device_id;

@@ -3,7 +3,7 @@
 #include <cstdlib>
 #include <string>
 #include <thread>
-#include "../../include/mm2amd.h"
+#include "capi_internal.hpp"
 namespace mm2amd {
 // The CPUs this process can really use: hardware threads, capped by the container's CPU quota (cgroup v2: /sys/fs/cgroup/cpu.max
 // "quota period"; v1: cpu.cfs_quota_us / cpu.cfs_period_us).  A 256-thread host with a 16-CPU quota runs 64 pool threads at a quarter of

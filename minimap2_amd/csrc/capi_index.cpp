@@ -10,7 +10,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include "../../include/mm2amd.h"
+#include "capi_internal.hpp"
 #include "device_ctx.hpp"
 #include "index_build.hpp"
 #include "index_handle.hpp"
@@ -20,12 +20,6 @@
 #include <map>
 
 namespace mm2amd {
-int capi_fail(int code, const std::string &msg);
-int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const std::vector<uint8_t> &hq, const std::vector<uint8_t> &ht, const uint32_t *dS,
-                 const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool, size_t pool_cap); // capi_kernels.cpp
-int junc_text_run(DeviceCtx &dc, const std::vector<RecJob> &jobs, const std::vector<RecHit> &hits, const std::vector<int> &slot, int n_res, const std::string &names,
-                  const std::string &tnames, const std::vector<uint64_t> &tname_off, const uint32_t *dS, const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool,
-                  size_t pool_cap); // capi_kernels.cpp
 struct IndexHandle {
 	FlatIndex fi;
 	DeviceIndexTables T;
@@ -48,10 +42,9 @@ mm2amd_index_t *mm2amd_idx_str(int w, int k, int is_hpc, int bucket_bits, int n,
 {
 	(void)bucket_bits; // the flat device table sizes its direct-address level from the number of distinct minimizers
 	if (n <= 0 || !seq) { capi_fail(MM2AMD_EINVAL, "[mm2amd] mm2amd_idx_str: need n > 0 sequences"); return nullptr; }
-	try {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+	mm2amd_index_t *out = nullptr;
+	guarded([&]() -> int {
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		std::unique_ptr<IndexHandle> h(new IndexHandle);
 		h->device = dc.device_id;
 		std::vector<uint64_t> lens(n);
@@ -60,14 +53,10 @@ mm2amd_index_t *mm2amd_idx_str(int w, int k, int is_hpc, int bucket_bits, int n,
 		if (is_hpc) flag |= ref::I_HPC;
 		if (!name) flag |= ref::I_NO_NAME;
 		DeviceIndexBuilder::build(h->fi, h->T, k, w, flag, n, seq, lens.data(), name, dc.stream);
-		return (mm2amd_index_t *)h.release();
-	} catch (const HipError &e) {
-		const std::string s = e.what();
-		capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
-	} catch (const std::exception &e) {
-		capi_fail(MM2AMD_EINVAL, e.what());
-	}
-	return nullptr;
+		out = (mm2amd_index_t *)h.release();
+		return 0;
+	});
+	return out;
 }
 
 void mm2amd_idx_destroy(mm2amd_index_t *idx) { delete (IndexHandle *)idx; }
@@ -108,9 +97,7 @@ int mm2amd_idx_export(const mm2amd_index_t *idx, uint32_t *bucket_start, uint64_
 	if (!idx) return capi_fail(MM2AMD_EINVAL, "[mm2amd] null index");
 	const IndexHandle *h = (const IndexHandle *)idx;
 	try {
-		DeviceCtx &dc = device_ctx(h->device);
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev(h->device);
 		if (bucket_start) HIP_CHECK(hipMemcpy(bucket_start, h->T.bucket_start.p, ((1ull << h->T.bucket_bits) + 1) * 4, hipMemcpyDeviceToHost));
 		if (keys && h->T.n_keys) HIP_CHECK(hipMemcpy(keys, h->T.keys.p, h->T.n_keys * 8, hipMemcpyDeviceToHost));
 		if (val_off) HIP_CHECK(hipMemcpy(val_off, h->T.val_off.p, (h->T.n_keys + 1) * 4, hipMemcpyDeviceToHost));
@@ -131,9 +118,7 @@ int mm2amd_idx_dump(const mm2amd_index_t *idx, const char *fn, int bucket_bits, 
 	FILE *fp = nullptr;
 	int rc = 0;
 	try {
-		DeviceCtx &dc = device_ctx(h->device);
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev(h->device); DeviceCtx &dc = dev.dc;
 		// what the format cannot hold is refused before the file is touched
 		if (bucket_bits <= 0) bucket_bits = 14;
 		if (bucket_bits > 2 * h->fi.k || bucket_bits > 28) throw std::invalid_argument("[mm2amd] index dump: bucket_bits must be in [1, 2k] and at most 28");
@@ -176,29 +161,22 @@ mm2amd_index_t *mm2amd_idx_load(const char *fn, int part, int *more)
 	const int fd = open(fn, O_RDONLY);
 	if (fd < 0) { capi_fail(MM2AMD_EIO, std::string("[mm2amd] index load: cannot open ") + fn + ": " + strerror(errno)); return nullptr; }
 	struct FdGuard { int fd; ~FdGuard() { close(fd); } } guard{fd};
-	try {
+	mm2amd_index_t *out = nullptr;
+	guarded([&]() -> int {
 		struct stat sb;
 		if (fstat(fd, &sb) != 0) throw IdxIoError(std::string("[mm2amd] index load: cannot stat ") + fn + ": " + strerror(errno));
 		const uint64_t file_size = (uint64_t)sb.st_size;
 		uint64_t off = 0;
 		for (int p = 0; p < part; ++p) off = DeviceIndexBuilder::skip_part(fd, file_size, off);
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		std::unique_ptr<IndexHandle> h(new IndexHandle);
 		h->device = dc.device_id;
 		const uint64_t end = DeviceIndexBuilder::load(h->fi, h->T, fd, file_size, off, dc.stream);
 		if (more) *more = end < file_size ? 1 : 0;
-		return (mm2amd_index_t *)h.release();
-	} catch (const IdxIoError &e) {
-		capi_fail(MM2AMD_EIO, e.what());
-	} catch (const HipError &e) {
-		const std::string s = e.what();
-		capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
-	} catch (const std::exception &e) {
-		capi_fail(MM2AMD_EINVAL, e.what());
-	}
-	return nullptr;
+		out = (mm2amd_index_t *)h.release();
+		return 0;
+	});
+	return out;
 }
 
 int mm2amd_idx_seq(const mm2amd_index_t *idx, uint32_t i, const char **name, uint32_t *len)
@@ -230,7 +208,7 @@ int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *co
 	const FlatIndex &fi = h->fi;
 	if ((fi.flag & ref::I_NO_SEQ) || !fi.S || !h->T.S.p) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_text_batch: the index holds no sequence");
 	if (n_hits == 0) return 0;
-	try {
+	return guarded([&]() -> int {
 		std::vector<TxtJob> tj(n_hits);
 		size_t qtot = 0, ctot = 0;
 		for (int i = 0; i < n_hits; ++i) {
@@ -262,16 +240,9 @@ int mm2amd_hits_text_batch(const mm2amd_index_t *idx, int n_hits, const void *co
 			if (tj[i].qlen) memcpy(&hq[tj[i].q_pos], qseq[i] + r->qs, (size_t)tj[i].qlen);
 			if (tj[i].n_cigar) memcpy(&cig[tj[i].cig_off], r->p->cigar, (size_t)tj[i].n_cigar * 4);
 		}
-		DeviceCtx &dc = device_ctx(h->device);
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
-		return aln_text_run(dc, tj, what, hq, ht, h->T.S.p, cig, res, pool, pool_cap);
-	} catch (const HipError &e) {
-		const std::string s = e.what();
-		return capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
-	} catch (const std::exception &e) {
-		return capi_fail(MM2AMD_EINVAL, e.what());
-	}
+		DeviceScope dev(h->device);
+		return aln_text_run(dev.dc, tj, what, hq, ht, h->T.S.p, cig, res, pool, pool_cap);
+	});
 }
 
 int mm2amd_hits_junc_batch(const mm2amd_index_t *idx, int n_hits, const void *const *hit, const char *const *qname, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
@@ -283,7 +254,7 @@ int mm2amd_hits_junc_batch(const mm2amd_index_t *idx, int n_hits, const void *co
 	if (fi.flag & ref::I_NO_NAME) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: the index holds no sequence names");
 	if ((fi.flag & ref::I_NO_SEQ) || !fi.S || !h->T.S.p) return capi_fail(MM2AMD_EINVAL, "[mm2amd] hits_junc_batch: the index holds no sequence");
 	if (n_hits == 0) return 0;
-	try {
+	return guarded([&]() -> int {
 		std::vector<RecJob> jobs;
 		std::vector<RecHit> hits;
 		std::vector<int> slot;
@@ -313,16 +284,9 @@ int mm2amd_hits_junc_batch(const mm2amd_index_t *idx, int n_hits, const void *co
 			cig.insert(cig.end(), r->p->cigar, r->p->cigar + r->p->n_cigar);
 			jobs.push_back(J), hits.push_back(o), slot.push_back(i);
 		}
-		DeviceCtx &dc = device_ctx(h->device);
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
-		return junc_text_run(dc, jobs, hits, slot, n_hits, names, tnames, tname_off, h->T.S.p, cig, res, pool, pool_cap);
-	} catch (const HipError &e) {
-		const std::string s = e.what();
-		return capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
-	} catch (const std::exception &e) {
-		return capi_fail(MM2AMD_EINVAL, e.what());
-	}
+		DeviceScope dev(h->device);
+		return junc_text_run(dev.dc, jobs, hits, slot, n_hits, names, tnames, tname_off, h->T.S.p, cig, res, pool, pool_cap);
+	});
 }
 
 int mm2amd_idx_io_stats(double *v, int n)

@@ -1,37 +1,28 @@
-// C ABI of libmm2amd.so (declared in include/mm2amd.h).
-#include <mutex>
-#include <string>
-#include <vector>
+// C ABI of libmm2amd.so (declared in include/mm2amd.h): the kernel-level entry points.
+#include <map>
 #include <cstring>
-#include "../../include/mm2amd.h"
-#include "hip_util.hpp"
+#include "capi_internal.hpp"
 #include "device_ctx.hpp"
 #include "ksw_host.hpp"
-#include "kernel_prof.hpp"
-#include "region_finish.hpp"
-#include "cigar_eqx.hpp"
+#include "stage_run.hpp"
+#include "ksw_ll.hpp"
 #include "aln_text.hpp"
 #include "junc_text.hpp"
-#include "ksw_ll.hpp"
-#include "sdust.hpp"
 #include "sdust_core.hpp"
-#include "hits_merge.hpp"
-#include "split_merge.hpp"
-#include "index_handle.hpp"
 #include "fastx.hpp"
+#include "tables.hpp"
 #include "threads.hpp"
 #include "trace.hpp"
 #include "device_sort.hpp"
 #include "seed_chain_dev.hpp"
-#include <map>
+#include "kernel_prof.hpp"
+#include "hits_merge.hpp"
+#include "split_merge.hpp"
+#include "index_handle.hpp"
 
-namespace mm2amd { int capi_fail(int code, const std::string &msg); }
 using namespace mm2amd;
-namespace mm2amd { extern const uint8_t kNt4Table[256]; }
 
 namespace {
-
-int fail(int code, const std::string &msg) { return capi_fail(code, msg); }
 
 struct KernelApiState { // buffers of the kernel-level entry points
 	KswRunner ksw;
@@ -65,19 +56,11 @@ struct SdustApiState { // mm2amd_sdust_batch: kept between calls
 };
 SdustApiState &sdust_state() { static SdustApiState s; return s; }
 
-bool sdust_no_narrow() { const char *e = getenv("MM2AMD_SDUST_NO_NARROW"); return e && *e && strcmp(e, "0") != 0; }
-int sdust_narrow_cap()
-{
-	const char *e = getenv("MM2AMD_SDUST_NARROW_CAP");
-	const long v = e && *e ? strtol(e, nullptr, 10) : kSdustNarrowCap;
-	return (int)(v < 1 ? 1 : v > kSdustWideCap ? kSdustWideCap : v);
-}
-
 int sdust_check_args(const char *who, int n_jobs, const mm2amd_sdust_job_t *jobs, int T, const mm2amd_sdust_res_t *res)
 {
-	if (n_jobs < 0 || T <= 0 || (n_jobs > 0 && (!jobs || !res))) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (T must be positive)");
+	if (n_jobs < 0 || T <= 0 || (n_jobs > 0 && (!jobs || !res))) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (T must be positive)");
 	for (int i = 0; i < n_jobs; ++i)
-		if (jobs[i].len < 0 || jobs[i].len > kSdustMaxLen || (jobs[i].len > 0 && !jobs[i].seq)) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad job (negative or excessive length, or null sequence)");
+		if (jobs[i].len < 0 || jobs[i].len > kSdustMaxLen || (jobs[i].len > 0 && !jobs[i].seq)) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad job (negative or excessive length, or null sequence)");
 	return 0;
 }
 
@@ -94,11 +77,11 @@ HitsMergeApiState &hm_state() { static HitsMergeApiState s; return s; }
 int hm_check_args(const char *who, int n_seg, const uint64_t *seg_off, const mm2amd_hm_hit_t *hits, const mm2amd_hm_opt_t *opt, const mm2amd_hm_out_t *out,
                   const mm2amd_hm_seg_t *seg)
 {
-	if (n_seg < 0 || (n_seg > 0 && (!seg_off || !opt || !seg))) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments");
+	if (n_seg < 0 || (n_seg > 0 && (!seg_off || !opt || !seg))) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments");
 	for (int s = 0; s < n_seg; ++s)
 		if (seg_off[s + 1] < seg_off[s] || seg_off[s + 1] - seg_off[s] > (uint64_t)kHmMaxHits)
-			return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad offsets (descending, or a segment above the hit limit)");
-	if (n_seg > 0 && seg_off[n_seg] > seg_off[0] && (!hits || !out)) return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": hits without arrays");
+			return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad offsets (descending, or a segment above the hit limit)");
+	if (n_seg > 0 && seg_off[n_seg] > seg_off[0] && (!hits || !out)) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": hits without arrays");
 	return 0;
 }
 
@@ -126,7 +109,7 @@ uint32_t fastx_long_line()
 int fastx_check_args(const char *who, const char *text, size_t len, size_t *n_recs, size_t *pool_len, size_t *consumed, int *path, size_t max_len)
 {
 	if (!n_recs || !pool_len || !consumed || !path || (len > 0 && !text) || len > max_len)
-		return fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (a null pointer, or a text above the length limit)");
+		return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments (a null pointer, or a text above the length limit)");
 	*n_recs = 0, *pool_len = 0, *consumed = 0, *path = MM2AMD_FASTX_PATH_HOST;
 	return 0;
 }
@@ -139,30 +122,14 @@ int fastx_host(const char *who, const char *text, size_t len, int is_final, int 
 	FastxSink out(sizing ? nullptr : recs, recs_cap, sizing ? nullptr : pool, pool_cap);
 	const size_t used = fastx_parse_host(text, len, is_final != 0, flags, out);
 	*n_recs = out.n_recs, *pool_len = out.pool_len, *consumed = !is_final && out.n_recs == 0 ? 0 : used;
-	if (!sizing && (out.n_recs > recs_cap || out.pool_len > pool_cap)) return fail(MM2AMD_ENOMEM, std::string("[mm2amd] ") + who + ": table or pool too small (a call with recs == NULL gives the sizes)");
+	if (!sizing && (out.n_recs > recs_cap || out.pool_len > pool_cap)) return capi_fail(MM2AMD_ENOMEM, std::string("[mm2amd] ") + who + ": table or pool too small (a call with recs == NULL gives the sizes)");
 	return 0;
-}
-
-template <typename F>
-int guarded(F &&f)
-{
-	try {
-		return f();
-	} catch (const HipError &e) {
-		std::string s = e.what();
-		return fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s);
-	} catch (const std::exception &e) {
-		return fail(MM2AMD_EINVAL, e.what());
-	}
 }
 
 } // namespace
 
 namespace mm2amd {
 
-// The two passes of aln_text_kernel around the host's offsets; shared by mm2amd_aln_text_batch and mm2amd_hits_text_batch (capi_index.cpp).
-// The caller holds dc.mu and has made the device current.  hq / ht: the jobs' byte pools (q_pos / t_pos of the kTxtQ* / kTxtTCodes sources
-// index them); dS: a packed reference already on the device (kTxtTPacked*), or null.
 int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const std::vector<uint8_t> &hq, const std::vector<uint8_t> &ht, const uint32_t *dS,
                  const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
 {
@@ -179,14 +146,10 @@ int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const
 	if (!cig.empty()) HIP_CHECK(hipMemcpyAsync(d_cig.p, cig.data(), cig.size() * 4, hipMemcpyHostToDevice, dc.stream));
 	HIP_CHECK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)n_jobs * sizeof(TxtJob), hipMemcpyHostToDevice, dc.stream));
 	TxtParams P;
-	P.jobs = d_jobs.p, P.n_jobs = n_jobs, P.what = what, P.qpool = d_q.p, P.tpool = d_t.p, P.S = dS, P.cigar = d_cig.p, P.res = d_res.p, P.off = nullptr, P.out = nullptr;
+	P.jobs = d_jobs.p, P.n_jobs = n_jobs, P.what = what, P.qpool = d_q.p, P.tpool = d_t.p, P.S = dS, P.cigar = d_cig.p, P.res = d_res.p;
 	KernelProfiler &prof = kernel_profiler(0);
-	prof.begin(dc.stream);
-	aln_text_launch(P, false, dc.stream);
-	prof.end(dc.stream, "aln_text_kernel[size]", 0.0, 0.0);
 	std::vector<TxtRes> hr(n_jobs);
-	HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(TxtRes), hipMemcpyDeviceToHost, dc.stream));
-	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	text_size_pass(P, aln_text_launch, hr.data(), prof, "aln_text_kernel[size]", 0.0, 0.0, dc.stream, stream_sync);
 	std::vector<uint64_t> off(n_jobs);
 	uint64_t total = 0;
 	double cols = 0;
@@ -196,26 +159,12 @@ int aln_text_run(DeviceCtx &dc, const std::vector<TxtJob> &jobs, int what, const
 		total += hr[i].len, cols += (double)hr[i].cols;
 	}
 	prof.add_units("aln_text_kernel[size]", cols);
-	if (!pool || total > pool_cap || total == 0) {
-		prof.collect();
-		if (pool && total > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] alignment text: pool too small (a call with pool == NULL gives the lengths)");
-		return 0;
-	}
-	d_out.ensure(total, 1.0);
-	HIP_CHECK(hipMemcpyAsync(d_off.p, off.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, dc.stream));
-	P.off = d_off.p, P.out = d_out.p;
-	prof.begin(dc.stream);
-	aln_text_launch(P, true, dc.stream);
-	prof.end(dc.stream, "aln_text_kernel[write]", (double)total, cols);
-	HIP_CHECK(hipMemcpyAsync(pool, d_out.p, total, hipMemcpyDeviceToHost, dc.stream));
-	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	if (pool && total > pool_cap) { prof.collect(); return capi_fail(MM2AMD_ENOMEM, "[mm2amd] alignment text: pool too small (a call with pool == NULL gives the lengths)"); }
+	if (pool && total) text_write_pass(P, aln_text_launch, off.data(), d_off.p, d_out.ensure(total, 1.0), pool, total, prof, "aln_text_kernel[write]", (double)total, cols, dc.stream, stream_sync);
 	prof.collect();
 	return 0;
 }
 
-// The two passes of junc_text_kernel for mm2amd_hits_junc_batch (capi_index.cpp); the caller holds dc.mu and has made the device current.
-// jobs / hits: one of each per hit that can write, in hit order; slot[k]: the hit's place in res (n_res entries, the others get len 0, status 0);
-// names / tnames: the read and target names the jobs and hits point into (hits[k].rid indexes tname_off); dS: the handle's packed sequence.
 int junc_text_run(DeviceCtx &dc, const std::vector<RecJob> &jobs, const std::vector<RecHit> &hits, const std::vector<int> &slot, int n_res, const std::string &names,
                   const std::string &tnames, const std::vector<uint64_t> &tname_off, const uint32_t *dS, const std::vector<uint32_t> &cig, mm2amd_txt_res_t *res, char *pool,
                   size_t pool_cap)
@@ -239,14 +188,10 @@ int junc_text_run(DeviceCtx &dc, const std::vector<RecJob> &jobs, const std::vec
 	if (!cig.empty()) HIP_CHECK(hipMemcpyAsync(d_cig.p, cig.data(), cig.size() * 4, hipMemcpyHostToDevice, dc.stream));
 	RecParams P{};
 	P.jobs = d_jobs.p, P.n_jobs = n_jobs, P.hits = d_hits.p, P.flag = 0, P.names = d_names.p, P.qpool = nullptr, P.S = dS, P.cigar = d_cig.p;
-	P.tnames = d_tnames.p, P.tname_off = d_tname_off.p, P.tlen = nullptr, P.res = d_res.p, P.off = nullptr, P.out = nullptr;
+	P.tnames = d_tnames.p, P.tname_off = d_tname_off.p, P.tlen = nullptr, P.res = d_res.p;
 	KernelProfiler &prof = kernel_profiler(0);
-	prof.begin(dc.stream);
-	junc_text_launch(P, false, dc.stream);
-	prof.end(dc.stream, "junc_text_kernel[size]", (double)cig.size() * 4.0, (double)n_jobs);
 	std::vector<RecRes> hr(n_jobs);
-	HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(RecRes), hipMemcpyDeviceToHost, dc.stream));
-	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	text_size_pass(P, junc_text_launch, hr.data(), prof, "junc_text_kernel[size]", (double)cig.size() * 4.0, (double)n_jobs, dc.stream, stream_sync);
 	std::vector<uint64_t> off(n_jobs);
 	uint64_t total = 0;
 	for (int k = 0, i = 0; i < n_res; ++i) {
@@ -256,19 +201,9 @@ int junc_text_run(DeviceCtx &dc, const std::vector<RecJob> &jobs, const std::vec
 			total += hr[k].len, ++k;
 		}
 	}
-	if (!pool || total > pool_cap || total == 0) {
-		prof.collect();
-		if (pool && total > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] junction text: pool too small (a call with pool == NULL gives the lengths)");
-		return 0;
-	}
-	d_out.ensure(total, 1.0);
-	HIP_CHECK(hipMemcpyAsync(d_off.p, off.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, dc.stream));
-	P.off = d_off.p, P.out = d_out.p;
-	prof.begin(dc.stream);
-	junc_text_launch(P, true, dc.stream);
-	prof.end(dc.stream, "junc_text_kernel[write]", (double)total + (double)cig.size() * 4.0, (double)n_jobs);
-	HIP_CHECK(hipMemcpyAsync(pool, d_out.p, total, hipMemcpyDeviceToHost, dc.stream));
-	HIP_CHECK(hipStreamSynchronize(dc.stream));
+	if (pool && total > pool_cap) { prof.collect(); return capi_fail(MM2AMD_ENOMEM, "[mm2amd] junction text: pool too small (a call with pool == NULL gives the lengths)"); }
+	if (pool && total)
+		text_write_pass(P, junc_text_launch, off.data(), d_off.p, d_out.ensure(total, 1.0), pool, total, prof, "junc_text_kernel[write]", (double)total + (double)cig.size() * 4.0, (double)n_jobs, dc.stream, stream_sync);
 	prof.collect();
 	return 0;
 }
@@ -281,7 +216,7 @@ int mm2amd_device_count(void)
 {
 	int n = 0;
 	hipError_t e = hipGetDeviceCount(&n);
-	if (e != hipSuccess) return fail(MM2AMD_ENODEV, std::string("[mm2amd] hipGetDeviceCount: ") + hipGetErrorString(e));
+	if (e != hipSuccess) return capi_fail(MM2AMD_ENODEV, std::string("[mm2amd] hipGetDeviceCount: ") + hipGetErrorString(e));
 	return n;
 }
 
@@ -289,16 +224,14 @@ static int ksw_batch(int mode, int8_t noncan, int n_jobs, const mm2amd_ksw_job_t
                      int8_t gapo, int8_t gape, int8_t gapo2, int8_t gape2,
                      mm2amd_ksw_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap)
 {
-	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat || m != 5) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_extd2_batch: bad arguments (m must be 5)");
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat || m != 5) return capi_fail(MM2AMD_EINVAL, "[mm2amd] ksw_extd2_batch: bad arguments (m must be 5)");
 	if (n_jobs == 0) return 0;
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		KernelApiState &d = kstate();
 		d.ksw.n_cu = dc.n_cu;
 		std::vector<KswJob> dj(n_jobs);
-		size_t qtot = 0, ttot = 0, ctot = 0;
+		size_t qtot = 0, ttot = 0;
 		for (int i = 0; i < n_jobs; ++i) {
 			const mm2amd_ksw_job_t &j = jobs[i];
 			KswJob &o = dj[i];
@@ -307,7 +240,6 @@ static int ksw_batch(int mode, int8_t noncan, int n_jobs, const mm2amd_ksw_job_t
 			o.tag = (uint32_t)i, o.reserved = 0;
 			qtot += j.qlen > 0 ? j.qlen : 0, ttot += j.tlen > 0 ? j.tlen : 0;
 		}
-		(void)ctot;
 		std::vector<uint8_t> hq(qtot + 1), ht(ttot + 1);
 		for (int i = 0; i < n_jobs; ++i) {
 			if (jobs[i].qlen > 0) memcpy(&hq[dj[i].q_off], jobs[i].query, jobs[i].qlen);
@@ -326,7 +258,7 @@ static int ksw_batch(int mode, int8_t noncan, int n_jobs, const mm2amd_ksw_job_t
 		d.ksw.disable_fast = getenv("MM2AMD_KSW_EXACT_ONLY") != nullptr;
 		d.ksw.run(dj, d.d_qpool.p, d.d_tpool.p, nullptr, sc, r.data(), &cig, &n_cig, dc.stream);
 		kernel_profiler().collect();
-		if (n_cig > cigar_pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] ksw_extd2_batch: cigar_pool too small (sum(qlen+tlen) always suffices)");
+		if (n_cig > cigar_pool_cap) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] ksw_extd2_batch: cigar_pool too small (sum(qlen+tlen) always suffices)");
 		if (n_cig) memcpy(cigar_pool, cig, n_cig * sizeof(uint32_t));
 		for (int i = 0; i < n_jobs; ++i) {
 			mm2amd_ksw_res_t &o = res[i];
@@ -361,12 +293,10 @@ int mm2amd_ksw_exts2_batch(int n_jobs, const mm2amd_ksw_job_t *jobs, int8_t m, c
 static int update_extra_impl(bool eqx, int n_jobs, const mm2amd_fin_job_t *jobs, const int8_t *mat25, int8_t q, int8_t e, int log_gap,
                              mm2amd_fin_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_cap)
 {
-	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat25) return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: bad arguments");
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat25) return capi_fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: bad arguments");
 	if (n_jobs == 0) return 0;
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		std::vector<FinRegion> regs(n_jobs);
 		std::vector<FinPiece> pieces;
 		std::vector<uint32_t> cig;
@@ -374,23 +304,23 @@ static int update_extra_impl(bool eqx, int n_jobs, const mm2amd_fin_job_t *jobs,
 		uint32_t longest = 1;
 		for (int i = 0; i < n_jobs; ++i) {
 			const mm2amd_fin_job_t &j = jobs[i];
-			if (j.qlen < 0 || j.tlen < 0 || j.n_pieces < 0 || (j.n_pieces > 0 && (!j.piece || !j.piece_len))) return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: bad job");
+			if (j.qlen < 0 || j.tlen < 0 || j.n_pieces < 0 || (j.n_pieces > 0 && (!j.piece || !j.piece_len))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: bad job");
 			FinRegion &r = regs[i];
 			r.q_pos = qtot, r.t_pos = ttot, r.piece0 = (uint32_t)pieces.size(), r.n_pieces = (uint32_t)j.n_pieces, r.out_off = (uint32_t)out_words;
 			r.q_len = j.qlen, r.t_len = j.tlen;
 			uint32_t sum = 0;
 			for (int k = 0; k < j.n_pieces; ++k) {
-				if (j.piece_len[k] < 0) return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: negative piece length");
+				if (j.piece_len[k] < 0) return capi_fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: negative piece length");
 				pieces.push_back(FinPiece{ (uint32_t)cig.size(), (uint32_t)j.piece_len[k] });
 				cig.insert(cig.end(), j.piece[k], j.piece[k] + j.piece_len[k]);
 				sum += (uint32_t)j.piece_len[k];
 			}
-			if (sum > (uint32_t)kFinMaxOps) return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: a region has more CIGAR operations than the kernel stages in LDS");
+			if (sum > (uint32_t)kFinMaxOps) return capi_fail(MM2AMD_EINVAL, "[mm2amd] update_extra_batch: a region has more CIGAR operations than the kernel stages in LDS");
 			longest = std::max(longest, sum);
 			out_words += sum;
 			qtot += ((size_t)j.qlen + 15) & ~(size_t)7, ttot += ((size_t)j.tlen + 15) & ~(size_t)7; // (the kernel reads aligned 8-byte / 8-code blocks)
 		}
-		if (!eqx && out_words > cigar_pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_batch: cigar_pool too small (the sum of the piece lengths suffices)");
+		if (!eqx && out_words > cigar_pool_cap) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_batch: cigar_pool too small (the sum of the piece lengths suffices)");
 		std::vector<uint8_t> hq(qtot + 16, 0);
 		std::vector<uint32_t> hS(ttot / 8 + 4, 0);
 		for (int i = 0; i < n_jobs; ++i) {
@@ -409,62 +339,35 @@ static int update_extra_impl(bool eqx, int n_jobs, const mm2amd_fin_job_t *jobs,
 		if (!cig.empty()) HIP_CHECK(hipMemcpyAsync(d_cig.p, cig.data(), cig.size() * 4, hipMemcpyHostToDevice, dc.stream));
 		HIP_CHECK(hipMemcpyAsync(d_regs.p, regs.data(), (size_t)n_jobs * sizeof(FinRegion), hipMemcpyHostToDevice, dc.stream));
 		if (!pieces.empty()) HIP_CHECK(hipMemcpyAsync(d_pieces.p, pieces.data(), pieces.size() * sizeof(FinPiece), hipMemcpyHostToDevice, dc.stream));
-		FinParams P;
-		P.regions = d_regs.p, P.n_regions = n_jobs, P.pieces = d_pieces.p, P.cigar_pool = d_cig.p, P.out_pool = d_out.p, P.results = d_res.p;
-		P.qpool = d_q.p, P.S = d_S.p;
-		memcpy(P.mat, mat25, 25);
-		P.q = q, P.e = e, P.log_gap = log_gap ? 1 : 0;
-		P.cap_ops = (int)std::min<uint32_t>((longest + 63) & ~63u, (uint32_t)kFinMaxOps);
-		region_finish_launch(P, dc.stream);
+		finish_run(d_regs.p, n_jobs, d_pieces.p, d_cig.p, d_out.p, d_res.p, d_q.p, d_S.p, mat25, q, e, log_gap != 0, longest, dc.stream, nullptr, 0.0, 0.0); // (no profile entry)
 		std::vector<FinResult> hr(n_jobs);
+		const auto put = [&](int i, int32_t n_cigar, uint32_t off) { // the public record from the kernel's
+			const FinResult &f = hr[i];
+			mm2amd_fin_res_t &o = res[i];
+			o.n_cigar = n_cigar, o.blen = f.blen, o.mlen = f.mlen, o.n_ambi = f.n_ambi, o.dp_max = f.dp_max, o.qshift = f.qshift, o.tshift = f.tshift, o.is_spliced = f.is_spliced, o.cigar_off = off;
+		};
 		if (eqx) { // count, place, write (cigar_eqx.hpp); cigar_pool null: the counts alone
-			DevBuf<uint32_t> d_n, d_eqx;
-			DevBuf<uint64_t> d_off;
+			EqxBufs B;
 			EqxParams X{};
 			X.regions = d_regs.p, X.n_regions = n_jobs, X.results = d_res.p, X.fin_pool = d_out.p, X.qpool = d_q.p, X.S = d_S.p;
-			X.n_ops = d_n.ensure(n_jobs), X.out_off = d_off.ensure(n_jobs);
 			KernelProfiler &prof = kernel_profiler();
-			prof.begin(dc.stream);
-			cigar_eqx_launch(X, false, dc.stream);
-			prof.end(dc.stream, "cigar_eqx_kernel[count]", (double)out_words * 4.0 + (double)qtot + (double)ttot / 2 + (double)n_jobs * (sizeof(FinRegion) + sizeof(FinResult) + 4), (double)n_jobs);
-			std::vector<uint32_t> hn(n_jobs);
-			std::vector<uint64_t> hoff(n_jobs);
 			HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(FinResult), hipMemcpyDeviceToHost, dc.stream));
-			HIP_CHECK(hipMemcpyAsync(hn.data(), d_n.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, dc.stream));
-			HIP_CHECK(hipStreamSynchronize(dc.stream));
-			uint64_t total = 0;
-			for (int i = 0; i < n_jobs; ++i) {
-				const FinResult &f = hr[i];
-				mm2amd_fin_res_t &o = res[i];
-				o.n_cigar = f.n_cigar < 0 ? f.n_cigar : (int32_t)hn[i], o.blen = f.blen, o.mlen = f.mlen, o.n_ambi = f.n_ambi, o.dp_max = f.dp_max, o.qshift = f.qshift, o.tshift = f.tshift;
-				o.is_spliced = f.is_spliced, o.cigar_off = (uint32_t)total;
-				hoff[i] = total, total += hn[i];
-			}
-			if (total >= (1ull << 32)) { prof.collect(); return fail(MM2AMD_EINVAL, "[mm2amd] update_extra_eqx_batch: the batch's =/X CIGARs exceed 32-bit offsets"); }
+			const uint64_t total = eqx_count(B, X, prof, (double)out_words * 4.0 + (double)qtot + (double)ttot / 2 + (double)n_jobs * (sizeof(FinRegion) + sizeof(FinResult) + 4), dc.stream, stream_sync);
+			for (int i = 0; i < n_jobs; ++i) put(i, hr[i].n_cigar < 0 ? hr[i].n_cigar : (int32_t)B.h_n.p[i], (uint32_t)B.h_off.p[i]);
+			if (total >= (1ull << 32)) { prof.collect(); return capi_fail(MM2AMD_EINVAL, "[mm2amd] update_extra_eqx_batch: the batch's =/X CIGARs exceed 32-bit offsets"); }
 			if (!cigar_pool) { prof.collect(); return 0; }
-			if (total > cigar_pool_cap) { prof.collect(); return fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_eqx_batch: cigar_pool too small (a call with cigar_pool == NULL gives every res[i].n_cigar)"); }
-			HIP_CHECK(hipMemcpyAsync(d_off.p, hoff.data(), (size_t)n_jobs * 8, hipMemcpyHostToDevice, dc.stream));
-			X.out_pool = d_eqx.ensure(total + 1);
-			prof.begin(dc.stream);
-			cigar_eqx_launch(X, true, dc.stream);
-			prof.end(dc.stream, "cigar_eqx_kernel[write]", ((double)out_words + (double)total) * 4.0 + 2.0 * ((double)qtot + (double)ttot / 2) + (double)n_jobs * (sizeof(FinRegion) + sizeof(FinResult) + 12), (double)n_jobs);
-			std::vector<uint32_t> he(total + 1);
-			if (total) HIP_CHECK(hipMemcpyAsync(he.data(), d_eqx.p, total * 4, hipMemcpyDeviceToHost, dc.stream));
-			HIP_CHECK(hipStreamSynchronize(dc.stream));
+			if (total > cigar_pool_cap) { prof.collect(); return capi_fail(MM2AMD_ENOMEM, "[mm2amd] update_extra_eqx_batch: cigar_pool too small (a call with cigar_pool == NULL gives every res[i].n_cigar)"); }
+			const EqxOut x = eqx_write(B, X, total, prof, ((double)out_words + (double)total) * 4.0 + 2.0 * ((double)qtot + (double)ttot / 2) + (double)n_jobs * (sizeof(FinRegion) + sizeof(FinResult) + 12), dc.stream);
+			stream_sync(dc.stream);
 			prof.collect();
-			if (total) memcpy(cigar_pool, he.data(), total * 4);
+			if (total) memcpy(cigar_pool, x.cigars, total * 4);
 			return 0;
 		}
 		std::vector<uint32_t> ho(out_words + 1);
 		HIP_CHECK(hipMemcpyAsync(hr.data(), d_res.p, (size_t)n_jobs * sizeof(FinResult), hipMemcpyDeviceToHost, dc.stream));
 		if (out_words) HIP_CHECK(hipMemcpyAsync(ho.data(), d_out.p, out_words * 4, hipMemcpyDeviceToHost, dc.stream));
 		HIP_CHECK(hipStreamSynchronize(dc.stream));
-		for (int i = 0; i < n_jobs; ++i) {
-			const FinResult &f = hr[i];
-			mm2amd_fin_res_t &o = res[i];
-			o.n_cigar = f.n_cigar, o.blen = f.blen, o.mlen = f.mlen, o.n_ambi = f.n_ambi, o.dp_max = f.dp_max, o.qshift = f.qshift, o.tshift = f.tshift, o.is_spliced = f.is_spliced;
-			o.cigar_off = regs[i].out_off;
-		}
+		for (int i = 0; i < n_jobs; ++i) put(i, hr[i].n_cigar, regs[i].out_off);
 		if (out_words) memcpy(cigar_pool, ho.data(), out_words * 4);
 		return 0;
 	});
@@ -484,7 +387,7 @@ int mm2amd_update_extra_eqx_batch(int n_jobs, const mm2amd_fin_job_t *jobs, cons
 
 int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm2amd_txt_res_t *res, char *pool, size_t pool_cap)
 {
-	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_DS_LONG) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad arguments");
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || what < MM2AMD_TXT_CIGAR || what > MM2AMD_TXT_DS_LONG) return capi_fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad arguments");
 	if (n_jobs == 0) return 0;
 	return guarded([&]() -> int {
 		const bool seqs = what != MM2AMD_TXT_CIGAR;
@@ -492,8 +395,8 @@ int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm
 		size_t qtot = 0, ttot = 0, ctot = 0;
 		for (int i = 0; i < n_jobs; ++i) {
 			const mm2amd_txt_job_t &j = jobs[i];
-			if (j.n_cigar < 0 || (j.n_cigar > 0 && !j.cigar)) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad job");
-			if (seqs && (j.qlen < 0 || j.tlen < 0 || (j.qlen > 0 && !j.query) || (j.tlen > 0 && !j.target))) return fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad job");
+			if (j.n_cigar < 0 || (j.n_cigar > 0 && !j.cigar)) return capi_fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad job");
+			if (seqs && (j.qlen < 0 || j.tlen < 0 || (j.qlen > 0 && !j.query) || (j.tlen > 0 && !j.target))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] aln_text_batch: bad job");
 			TxtJob &o = tj[i];
 			o.q_pos = qtot, o.t_pos = ttot, o.cig_off = ctot, o.n_cigar = (uint32_t)j.n_cigar, o.qlen = seqs ? j.qlen : 0, o.tlen = seqs ? j.tlen : 0;
 			o.qsrc = (uint8_t)kTxtQCodes, o.tsrc = (uint8_t)kTxtTCodes, o.reserved = 0;
@@ -508,10 +411,8 @@ int mm2amd_aln_text_batch(int n_jobs, const mm2amd_txt_job_t *jobs, int what, mm
 			if (seqs && j.qlen) memcpy(&hq[tj[i].q_pos], j.query, (size_t)j.qlen);
 			if (seqs && j.tlen) memcpy(&ht[tj[i].t_pos], j.target, (size_t)j.tlen);
 		}
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
-		return aln_text_run(dc, tj, what, hq, ht, nullptr, cig, res, pool, pool_cap);
+		DeviceScope dev;
+		return aln_text_run(dev.dc, tj, what, hq, ht, nullptr, cig, res, pool, pool_cap);
 	});
 }
 
@@ -526,20 +427,18 @@ int mm2amd_ksw_ll_limits(int *strip_cols, int *wg_waves, int64_t *wg_min_cells, 
 
 int mm2amd_ksw_ll_batch(int n_jobs, const mm2amd_ll_job_t *jobs, int8_t m, const int8_t *mat, int gapo, int gape, mm2amd_ll_res_t *res)
 {
-	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat || m != 5) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: bad arguments (m must be 5)");
+	if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !mat || m != 5) return capi_fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: bad arguments (m must be 5)");
 	if (n_jobs == 0) return 0;
 	for (int i = 0; i < n_jobs; ++i) {
 		const mm2amd_ll_job_t &j = jobs[i];
-		if (j.qlen < 0 || j.tlen < 0 || (j.qlen > 0 && !j.query) || (j.tlen > 0 && !j.target)) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: bad job (negative length or null sequence)");
+		if (j.qlen < 0 || j.tlen < 0 || (j.qlen > 0 && !j.query) || (j.tlen > 0 && !j.target)) return capi_fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: bad job (negative length or null sequence)");
 		uint8_t top = 0;
 		for (int32_t k = 0; k < j.qlen; ++k) top |= (uint8_t)(j.query[k] > 4);
 		for (int32_t k = 0; k < j.tlen; ++k) top |= (uint8_t)(j.target[k] > 4);
-		if (top) return fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: a sequence holds a code above 4");
+		if (top) return capi_fail(MM2AMD_EINVAL, "[mm2amd] ksw_ll_batch: a sequence holds a code above 4");
 	}
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		LlApiState &d = ll_state();
 		const bool no_wg = ll_no_wg();
 		const int64_t wg_min = ll_wg_min_cells();
@@ -630,7 +529,7 @@ int mm2amd_ksw_ll_batch(int n_jobs, const mm2amd_ll_job_t *jobs, int8_t m, const
 
 int mm2amd_sdust_limits(int *narrow_cap, int *wide_cap, int *max_len)
 {
-	if (narrow_cap) *narrow_cap = sdust_narrow_cap();
+	if (narrow_cap) *narrow_cap = sdust_env_narrow_cap();
 	if (wide_cap) *wide_cap = kSdustWideCap;
 	if (max_len) *max_len = kSdustMaxLen;
 	return 0;
@@ -641,9 +540,7 @@ int mm2amd_sdust_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, mm2amd
 	if (const int rc = sdust_check_args("sdust_batch", n_jobs, jobs, T, res)) return rc;
 	if (n_jobs == 0) return 0;
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		SdustApiState &d = sdust_state();
 		const size_t n = (size_t)n_jobs;
 		uint64_t *const h_off = d.h_off.ensure(2 * (n + 1)); // the jobs' base offsets, then their offsets in the pool
@@ -665,30 +562,21 @@ int mm2amd_sdust_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, mm2amd
 		memset(&hc, 0, sizeof hc);
 		uint32_t *const h_list = d.h_list.ensure(2 * n); // the listed jobs, then every job's number of regions
 		for (size_t i = 0; i < n; ++i) res[i].path = MM2AMD_SDUST_PATH_NARROW;
-		if (sdust_no_narrow()) {
-			P.cap = kSdustWideCap, P.wide = 2;
-			prof.begin(dc.stream);
-			sdust_launch(P, 0, dc.stream);
-			prof.end(dc.stream, "sdust_kernel[wide]", 0.0, (double)total);
+		if (sdust_env_no_narrow()) {
+			sdust_run_class(P, 2, 0, prof, (double)total, dc.stream);
 			for (size_t i = 0; i < n; ++i) res[i].path = MM2AMD_SDUST_PATH_WIDE;
 		} else {
-			P.cap = sdust_narrow_cap(), P.wide = 0;
-			prof.begin(dc.stream);
-			sdust_launch(P, 0, dc.stream);
-			prof.end(dc.stream, "sdust_kernel[narrow]", 0.0, 0.0);
+			sdust_run_class(P, 0, 0, prof, 0.0, dc.stream);
 			HIP_CHECK(hipMemcpyAsync(&hc, d.d_cnt.p, sizeof hc, hipMemcpyDeviceToHost, dc.stream));
 			HIP_CHECK(hipStreamSynchronize(dc.stream));
-			if (hc.n_wide > (uint32_t)n_jobs) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: the device's list of wide jobs is longer than the batch");
+			if (hc.n_wide > (uint32_t)n_jobs) return capi_fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: the device's list of wide jobs is longer than the batch");
 			double wide_bases = 0;
 			if (hc.n_wide) { // the jobs that stopped, scanned again with the full list: a launch of exactly that many wavefronts
 				HIP_CHECK(hipMemcpyAsync(h_list, d.d_list.p, (size_t)hc.n_wide * 4, hipMemcpyDeviceToHost, dc.stream));
-				P.cap = kSdustWideCap, P.wide = 1;
-				prof.begin(dc.stream);
-				sdust_launch(P, (int)std::min<uint32_t>(hc.n_wide, (uint32_t)kSdustWideGrid), dc.stream);
-				prof.end(dc.stream, "sdust_kernel[wide]", 0.0, 0.0);
+				sdust_run_class(P, 1, (int)std::min<uint32_t>(hc.n_wide, (uint32_t)kSdustWideGrid), prof, 0.0, dc.stream);
 				HIP_CHECK(hipStreamSynchronize(dc.stream));
 				for (uint32_t k = 0; k < hc.n_wide; ++k) {
-					if (h_list[k] >= (uint32_t)n_jobs) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: the device listed a job outside the batch");
+					if (h_list[k] >= (uint32_t)n_jobs) return capi_fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: the device listed a job outside the batch");
 					res[h_list[k]].path = MM2AMD_SDUST_PATH_WIDE, wide_bases += (double)jobs[h_list[k]].len;
 				}
 				prof.add_units("sdust_kernel[wide]", wide_bases);
@@ -702,16 +590,16 @@ int mm2amd_sdust_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, mm2amd
 		HIP_CHECK(hipMemcpyAsync(&hc, d.d_cnt.p, sizeof hc, hipMemcpyDeviceToHost, dc.stream));
 		HIP_CHECK(hipStreamSynchronize(dc.stream));
 		prof.collect();
-		if (hc.err) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: a list of perfect intervals outgrew the wide capacity");
+		if (hc.err) return capi_fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: a list of perfect intervals outgrew the wide capacity");
 		uint64_t *const out_off = h_off + n + 1;
 		uint64_t n_out = 0;
 		for (size_t i = 0; i < n; ++i) {
-			if (h_n[i] > (uint32_t)jobs[i].len) return fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: more regions than bases");
+			if (h_n[i] > (uint32_t)jobs[i].len) return capi_fail(MM2AMD_EHIP, "[mm2amd] sdust_batch: more regions than bases");
 			out_off[i] = n_out, res[i].off = n_out, res[i].n = h_n[i];
 			n_out += h_n[i];
 		}
 		if (!pool || n_out == 0) return 0;
-		if (n_out > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] sdust_batch: pool too small (a call with pool == NULL gives the counts)");
+		if (n_out > pool_cap) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] sdust_batch: pool too small (a call with pool == NULL gives the counts)");
 		d.d_out.ensure(n_out);
 		HIP_CHECK(hipMemcpyAsync(d.d_out_off.p, out_off, n * 8, hipMemcpyHostToDevice, dc.stream));
 		sdust_pack_launch(P, d.d_out_off.p, d.d_out.p, dc.stream);
@@ -744,7 +632,7 @@ int mm2amd_sdust_host_batch(int n_jobs, const mm2amd_sdust_job_t *jobs, int T, i
 		for (int i = 0; i < n_jobs; ++i) res[i].off = n_out, res[i].n = (uint32_t)regs[i].size(), res[i].path = -1, n_out += regs[i].size();
 		if (core_seconds) for (double b : busy) *core_seconds += b;
 		if (!pool || n_out == 0) return 0;
-		if (n_out > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] sdust_host_batch: pool too small (a call with pool == NULL gives the counts)");
+		if (n_out > pool_cap) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] sdust_host_batch: pool too small (a call with pool == NULL gives the counts)");
 		for (int i = 0; i < n_jobs; ++i) if (!regs[i].empty()) memcpy(pool + res[i].off, regs[i].data(), regs[i].size() * 8);
 		return 0;
 	});
@@ -764,9 +652,7 @@ int mm2amd_hits_merge_batch(int n_seg, const uint64_t *seg_off, const mm2amd_hm_
 	if (const int rc = hm_check_args("hits_merge_batch", n_seg, seg_off, hits, opt, out, seg)) return rc;
 	if (n_seg == 0) return 0;
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		HitsMergeApiState &d = hm_state();
 		const size_t n = (size_t)n_seg;
 		const uint64_t first = seg_off[0], total = seg_off[n] - first;
@@ -810,7 +696,7 @@ int mm2amd_hits_merge_batch(int n_seg, const uint64_t *seg_off, const mm2amd_hm_
 		std::vector<uint32_t> host_list;
 		for (size_t s = 0; s < n; ++s) {
 			if (seg[s].path == MM2AMD_HM_PATH_HOST) { host_list.push_back((uint32_t)s); continue; }
-			if (seg[s].n_kept < 0 || (uint64_t)seg[s].n_kept > seg_off[s + 1] - seg_off[s]) return fail(MM2AMD_EHIP, "[mm2amd] hits_merge_batch: the device kept more hits than the segment has");
+			if (seg[s].n_kept < 0 || (uint64_t)seg[s].n_kept > seg_off[s + 1] - seg_off[s]) return capi_fail(MM2AMD_EHIP, "[mm2amd] hits_merge_batch: the device kept more hits than the segment has");
 		}
 		parallel_for(effective_cpus(), (long)host_list.size(), [&](long k, int) {
 			const uint32_t s = host_list[(size_t)k];
@@ -841,14 +727,14 @@ int mm2amd_hits_merge_host_batch(int n_seg, const uint64_t *seg_off, const mm2am
 void *mm2amd_split_open(const char *prefix, const mm2amd_index_t *idx, int part_no)
 {
 	void *h = nullptr;
-	if (!prefix || !idx || part_no < 0 || part_no > 9999) { fail(MM2AMD_EINVAL, "[mm2amd] split_open: bad arguments"); return nullptr; }
+	if (!prefix || !idx || part_no < 0 || part_no > 9999) { capi_fail(MM2AMD_EINVAL, "[mm2amd] split_open: bad arguments"); return nullptr; }
 	guarded([&]() -> int { h = split_open(prefix, index_flat((const IndexHandle *)idx), part_no); return 0; });
 	return h;
 }
 
 int mm2amd_split_write(void *w, const void *opt, int n_seq, const int *n_reg, void *const *reg, const int *rep_len, const int *frag_gap)
 {
-	if (!w || !opt || n_seq < 0 || (n_seq > 0 && (!n_reg || !reg || !rep_len || !frag_gap))) return fail(MM2AMD_EINVAL, "[mm2amd] split_write: bad arguments");
+	if (!w || !opt || n_seq < 0 || (n_seq > 0 && (!n_reg || !reg || !rep_len || !frag_gap))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] split_write: bad arguments");
 	return guarded([&]() -> int {
 		SplitWriter &sw = *(SplitWriter *)w;
 		sw.cigar = (((const ref::MapOpt *)opt)->flag & ref::F_CIGAR) != 0;
@@ -865,13 +751,13 @@ int mm2amd_split_close(void *w)
 	sw->fp = nullptr;
 	const std::string fn = sw->fn;
 	delete sw;
-	return ok ? 0 : fail(MM2AMD_EIO, "[mm2amd] split_close: cannot finish " + fn);
+	return ok ? 0 : capi_fail(MM2AMD_EIO, "[mm2amd] split_close: cannot finish " + fn);
 }
 
 void *mm2amd_split_merge_open(const char *prefix, int n_parts, const void *opt)
 {
 	void *h = nullptr;
-	if (!prefix || !opt) { fail(MM2AMD_EINVAL, "[mm2amd] split_merge_open: bad arguments"); return nullptr; }
+	if (!prefix || !opt) { capi_fail(MM2AMD_EINVAL, "[mm2amd] split_merge_open: bad arguments"); return nullptr; }
 	guarded([&]() -> int {
 		SplitMerger *m = split_merge_open(prefix, n_parts, *(const ref::MapOpt *)opt);
 		m->device = split_device_route();
@@ -883,27 +769,27 @@ void *mm2amd_split_merge_open(const char *prefix, int n_parts, const void *opt)
 
 int mm2amd_split_merge_batch(void *h, int n_frag, const int *seg_off, const int *n_seg, const void *seq, int *n_reg, void **reg, int *rep_len, int *frag_gap)
 {
-	if (!h || n_frag < 0 || (n_frag > 0 && (!seq || !n_reg || !reg || !rep_len || !frag_gap))) return fail(MM2AMD_EINVAL, "[mm2amd] split_merge_batch: bad arguments");
+	if (!h || n_frag < 0 || (n_frag > 0 && (!seq || !n_reg || !reg || !rep_len || !frag_gap))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] split_merge_batch: bad arguments");
 	return guarded([&]() -> int { split_merge_batch(*(SplitMerger *)h, n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq, n_reg, reg, rep_len, frag_gap); return 0; });
 }
 
 int mm2amd_split_merge_format(void *h, int n_frag, const int *seg_off, const int *n_seg, const void *seq, const int *n_reg, void *const *reg, const int *rep_len, char **out,
                               size_t *out_len)
 {
-	if (!h || !out || !out_len || n_frag < 0 || (n_frag > 0 && (!seq || !n_reg || !reg))) return fail(MM2AMD_EINVAL, "[mm2amd] split_merge_format: bad arguments");
+	if (!h || !out || !out_len || n_frag < 0 || (n_frag > 0 && (!seq || !n_reg || !reg))) return capi_fail(MM2AMD_EINVAL, "[mm2amd] split_merge_format: bad arguments");
 	return guarded([&]() -> int {
 		SplitMerger &m = *(SplitMerger *)h;
 		*out = format_batch(m.fi, m.opt, effective_cpus(), n_frag, seg_off, n_seg, (const ref::Bseq1 *)seq, n_reg, reg, rep_len, out_len);
-		return *out ? 0 : fail(MM2AMD_ENOMEM, "[mm2amd] split_merge_format: out of memory");
+		return *out ? 0 : capi_fail(MM2AMD_ENOMEM, "[mm2amd] split_merge_format: out of memory");
 	});
 }
 
 int mm2amd_split_merge_sq(void *h, char **out, size_t *out_len)
 {
-	if (!h || !out || !out_len) return fail(MM2AMD_EINVAL, "[mm2amd] split_merge_sq: bad arguments");
+	if (!h || !out || !out_len) return capi_fail(MM2AMD_EINVAL, "[mm2amd] split_merge_sq: bad arguments");
 	return guarded([&]() -> int {
 		const std::string s = split_sq_lines(*(SplitMerger *)h);
-		if (!(*out = (char *)malloc(s.size() + 1))) return fail(MM2AMD_ENOMEM, "[mm2amd] split_merge_sq: out of memory");
+		if (!(*out = (char *)malloc(s.size() + 1))) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] split_merge_sq: out of memory");
 		memcpy(*out, s.c_str(), s.size() + 1);
 		*out_len = s.size();
 		return 0;
@@ -992,7 +878,7 @@ int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm
 		prof.collect();
 		if (!profiling) d.times[0] = Trace::now() - t0, t0 = Trace::now(); // (the upload is not timed apart then: it ends within this wait)
 		P.n_nl = hw[0];
-		if (P.n_nl > len) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: the device counted more lines than bytes");
+		if (P.n_nl > len) return capi_fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: the device counted more lines than bytes");
 		const uint32_t n_all = P.n_nl + (text[len - 1] != '\n' ? 1u : 0u);
 		if (fq) {
 			if (fin && (n_all & 3u)) return to_host(); // the file ends inside a record: what the reference makes of the rest is the host's business
@@ -1016,7 +902,7 @@ int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm
 		prof.collect();
 		if (hw[0]) return to_host(); // the buffer is not what its first byte promised
 		const uint32_t n_work = hw[1], total = hw[3];
-		if (n_work > P.work_cap) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: more long-line work items than the text can hold");
+		if (n_work > P.work_cap) return capi_fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: more long-line work items than the text can hold");
 		size_t used = len;
 		if (fq) {
 			P.n_rec = P.n_lines / 4, P.pool_len = total;
@@ -1026,17 +912,17 @@ int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm
 		} else { // the last header opens the record the buffer does not complete
 			P.n_rec = hw[4] - 1;
 			const uint32_t last = hw[2];
-			if (last >= P.n_lines) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: the device's last header lies outside the line table");
+			if (last >= P.n_lines) return capi_fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: the device's last header lies outside the line table");
 			HIP_CHECK(hipMemcpyAsync(hw + 6, P.dst + last, 4, hipMemcpyDeviceToHost, st));
 			HIP_CHECK(hipMemcpyAsync(hw + 7, P.line_off + last, 4, hipMemcpyDeviceToHost, st));
 			stream_wait(st);
 			P.pool_len = P.n_rec ? hw[6] + 1 : 0, used = P.n_rec ? hw[7] : 0;
 		}
-		if (used > len || P.pool_len > len + 1 || (size_t)P.n_rec > len) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: sizes from the device exceed the text");
+		if (used > len || P.pool_len > len + 1 || (size_t)P.n_rec > len) return capi_fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: sizes from the device exceed the text");
 		d.times[1] = Trace::now() - t0, t0 = Trace::now();
 		*path = P.cls, *n_recs = P.n_rec, *pool_len = P.pool_len, *consumed = used;
 		if (!recs || !pool || P.n_rec == 0) return 0;
-		if (P.n_rec > recs_cap || P.pool_len > pool_cap) return fail(MM2AMD_ENOMEM, "[mm2amd] fastx_parse: table or pool too small (a call with recs == NULL gives the sizes)");
+		if (P.n_rec > recs_cap || P.pool_len > pool_cap) return capi_fail(MM2AMD_ENOMEM, "[mm2amd] fastx_parse: table or pool too small (a call with recs == NULL gives the sizes)");
 		P.pool = d.d_pool.ensure((size_t)total + 16), P.recs = d.d_recs.ensure(P.n_rec);
 		FastxDevRec *const hr = d.h_recs.ensure(P.n_rec);
 		prof.begin(st); fastx_copy_launch(P, false, 0, st); prof.end(st, "fastx_copy_kernel[short]", (double)len + (double)P.pool_len, (double)P.n_lines);
@@ -1052,7 +938,7 @@ int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm
 			const FastxDevRec &s = hr[r];
 			mm2amd_fastx_rec_t &o = recs[r];
 			const uint32_t l_seq = fq ? s.l_seq : (r + 1 < P.n_rec ? hr[r + 1].name : P.pool_len) - 1u - s.seq;
-			if (s.name >= P.pool_len || s.seq >= P.pool_len || (uint64_t)s.seq + l_seq >= P.pool_len) return fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: a record from the device lies outside the pool");
+			if (s.name >= P.pool_len || s.seq >= P.pool_len || (uint64_t)s.seq + l_seq >= P.pool_len) return capi_fail(MM2AMD_EHIP, "[mm2amd] fastx_parse: a record from the device lies outside the pool");
 			o.name = s.name, o.name_len = s.name_len, o.comment_len = s.comment_len, o.comment = s.comment_len ? (uint64_t)s.name + s.name_len + 1 : UINT64_MAX;
 			o.seq = s.seq, o.l_seq = (int32_t)l_seq, o.qual = fq && with_qual ? (uint64_t)s.seq + l_seq + 1 : UINT64_MAX, o.reserved = 0;
 		}
@@ -1063,12 +949,10 @@ int mm2amd_fastx_parse(const char *text, size_t len, int is_final, int flags, mm
 
 int mm2amd_sort_pairs_u64(uint64_t *keys, uint64_t *vals, uint64_t n, int bits)
 {
-	if ((n > 0 && (!keys || !vals)) || bits < 0 || bits > 64 || n >= (1ull << 32)) return fail(MM2AMD_EINVAL, "[mm2amd] sort_pairs_u64: bad arguments (n < 2^32, 0 <= bits <= 64)");
+	if ((n > 0 && (!keys || !vals)) || bits < 0 || bits > 64 || n >= (1ull << 32)) return capi_fail(MM2AMD_EINVAL, "[mm2amd] sort_pairs_u64: bad arguments (n < 2^32, 0 <= bits <= 64)");
 	if (n == 0) return 0;
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		DevBuf<uint64_t> k0, v0, k1, v1;
 		k0.ensure(n, 1.0), v0.ensure(n, 1.0), k1.ensure(n, 1.0), v1.ensure(n, 1.0);
 		HIP_CHECK(hipMemcpyAsync(k0.p, keys, n * 8, hipMemcpyHostToDevice, dc.stream));
@@ -1083,11 +967,9 @@ int mm2amd_sort_pairs_u64(uint64_t *keys, uint64_t *vals, uint64_t n, int bits)
 
 int mm2amd_exclusive_sum_u32(const uint32_t *in, uint32_t *out, uint64_t n)
 {
-	if (!out || (n > 0 && !in) || n >= (1ull << 32)) return fail(MM2AMD_EINVAL, "[mm2amd] exclusive_sum_u32: bad arguments (n < 2^32)");
+	if (!out || (n > 0 && !in) || n >= (1ull << 32)) return capi_fail(MM2AMD_EINVAL, "[mm2amd] exclusive_sum_u32: bad arguments (n < 2^32)");
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		DevBuf<uint32_t> d;
 		d.ensure(n + 1, 1.0);
 		if (n) HIP_CHECK(hipMemcpyAsync(d.p, in, n * 4, hipMemcpyHostToDevice, dc.stream));
@@ -1102,12 +984,12 @@ int mm2amd_encode_batch(int n, const char *const *seqs, const int32_t *lens, con
 
 int mm2amd_encode_range(int n, const char *const *seqs, const int32_t *lens, const int32_t *lens2, int lo, int hi, uint8_t *out)
 {
-	if (n < 0 || !out || (n > 0 && (!seqs || !lens)) || lo < 0 || hi < lo || hi > n) return fail(MM2AMD_EINVAL, "[mm2amd] encode_batch: bad arguments");
+	if (n < 0 || !out || (n > 0 && (!seqs || !lens)) || lo < 0 || hi < lo || hi > n) return capi_fail(MM2AMD_EINVAL, "[mm2amd] encode_batch: bad arguments");
 	std::vector<uint64_t> unit_off(1, 0); // as begin_batch lays a batch out: units back to back, a pair's mate right after its first read
 	std::vector<size_t> frag_unit(1, 0);  // fragment i's first unit
 	for (int i = 0; i < n; ++i) {
 		const int32_t l2 = lens2 ? lens2[i] : 0;
-		if (lens[i] < 0 || l2 < 0 || (lens[i] + (int64_t)l2 > 0 && !seqs[i])) return fail(MM2AMD_EINVAL, "[mm2amd] encode_batch: bad read (negative length or null sequence)");
+		if (lens[i] < 0 || l2 < 0 || (lens[i] + (int64_t)l2 > 0 && !seqs[i])) return capi_fail(MM2AMD_EINVAL, "[mm2amd] encode_batch: bad read (negative length or null sequence)");
 		unit_off.push_back(unit_off.back() + (uint64_t)lens[i]);
 		if (l2 > 0) unit_off.push_back(unit_off.back() + (uint64_t)l2);
 		frag_unit.push_back(unit_off.size() - 1);
@@ -1115,9 +997,7 @@ int mm2amd_encode_range(int n, const char *const *seqs, const int32_t *lens, con
 	const uint64_t total = unit_off.back();
 	const size_t n_units = unit_off.size() - 1;
 	return guarded([&]() -> int {
-		DeviceCtx &dc = device_ctx();
-		std::lock_guard<std::mutex> lk(dc.mu);
-		ensure_device(dc);
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
 		PinBuf<char> h_ascii;
 		DevBuf<uint8_t> d_pool;
 		DevBuf<uint64_t> d_off;

@@ -10,26 +10,11 @@
 #include <shared_mutex>
 #include <string>
 #include <thread>
-#include "../../include/mm2amd.h"
+#include "capi_internal.hpp"
 #include "mapper.hpp"
 #include "format.hpp"
 #include "index_handle.hpp"
 #include "threads.hpp"
-
-namespace mm2amd {
-int effective_cpus(); // capi_common.cpp
-// backend_hip.cpp in the product: `device` < 0 = the process's default device; `replica` numbers the backends of one context;
-// `tables_device` is where `device_tables` live (a backend on another device copies them)
-Backend *make_backend(const FlatIndex &fi, void *device_tables, int n_threads, int device, int replica, int tables_device);
-int backend_device_count();
-// The minimizer tables of `fi` (sequence table and packed sequence set) built by the backend on `device` (< 0: the default one);
-// returns the tables (for make_backend's device_tables; *on_device = their device) or nullptr when this backend wants host tables.
-void *backend_build_index_tables(FlatIndex &fi, int device, int *on_device);
-void backend_free_index_tables(void *tables);
-const char *backend_name();
-void capi_set_error(const std::string &msg);              // capi_common.cpp
-int capi_fail(int code, const std::string &msg);
-}
 
 using namespace mm2amd;
 

@@ -1,5 +1,7 @@
 #include <cstdlib>
 #include "device_ctx.hpp"
+#include "capi_internal.hpp"
+#include "index_build.hpp"
 #include "kernel_prof.hpp"
 
 namespace mm2amd {
@@ -22,8 +24,6 @@ int default_device()
 	if (id < 0 || id >= n) throw HipError("[mm2amd] MM2AMD_DEVICE names a device this process cannot see");
 	return id;
 }
-
-void apply_hw_queue_default(); // capi_common.cpp
 
 DeviceCtx &device_ctx(int id)
 {
@@ -51,6 +51,14 @@ void ensure_device(DeviceCtx &d)
 	d.n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 	HIP_CHECK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
 	d.ready = true;
+}
+
+int capi_fail_current()
+{
+	try { throw; }
+	catch (const IdxIoError &e) { return capi_fail(MM2AMD_EIO, e.what()); }
+	catch (const HipError &e) { const std::string s = e.what(); return capi_fail(s.find("no HIP device") != std::string::npos ? MM2AMD_ENODEV : MM2AMD_EHIP, s); }
+	catch (const std::exception &e) { return capi_fail(MM2AMD_EINVAL, e.what()); }
 }
 
 } // namespace mm2amd

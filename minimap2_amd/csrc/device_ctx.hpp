@@ -20,4 +20,11 @@ DeviceCtx &device_ctx(int id = -1);   // -1: default_device()
 // up; throws HipError("... no HIP device ...") when there is none.
 void ensure_device(DeviceCtx &d);
 
+// An entry point's hold on a device: the context, its mutex, the device made current -- for as long as the object lives.
+struct DeviceScope {
+	DeviceCtx &dc;
+	std::lock_guard<std::mutex> lk;
+	explicit DeviceScope(int id = -1) : dc(device_ctx(id)), lk(dc.mu) { ensure_device(dc); }
+};
+
 } // namespace mm2amd

@@ -2,6 +2,7 @@
 #include <cstring>
 #include <stdexcept>
 #include "flat_index.hpp"
+#include "tables.hpp"
 
 namespace mm2amd {
 
@@ -95,7 +96,6 @@ void FlatIndex::from_sequences(int k_, int w_, int flag_, int n, const char *con
 	S_own.assign((sum_len + 7) / 8, 0);
 	std::vector<std::pair<uint64_t, uint64_t>> pairs;
 	std::vector<ref::mm128> mz;
-	extern const uint8_t kNt4Table[256];
 	for (int i = 0; i < n; ++i) {
 		for (uint32_t j = 0; j < seq_len[i]; ++j) {
 			const uint64_t o = seq_off[i] + j;

@@ -21,6 +21,7 @@
 #include "aln_text.hpp"
 #include "threads.hpp"
 #include "host_prof.hpp"
+#include "tables.hpp"
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -28,8 +29,6 @@
 namespace mm2amd {
 
 using namespace ref;
-
-extern const uint8_t kNt4Table[256];
 
 namespace {
 

@@ -77,9 +77,6 @@ inline void stream_wait(hipStream_t s)
 	}
 }
 
-// CPUs this process may actually use: the smaller of the hardware thread count and the container's CPU quota (cgroup v2 cpu.max, v1 cfs quota)
-int effective_cpus(); // capi_common.cpp
-
 struct AllocStats { std::atomic<long> dev_allocs{0}, pin_allocs{0}; std::atomic<double> dummy{0}; std::atomic<long long> dev_bytes{0}, pin_bytes{0}; std::atomic<long long> ns{0}; };
 inline AllocStats &alloc_stats() { static AllocStats s; return s; }
 // how the banded gap-fill kernel's launch classes fared since the process started (ksw_host.cpp): windows tried in 128 / 256 diagonals, sent on to the wider

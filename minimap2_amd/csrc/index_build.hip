@@ -23,10 +23,10 @@
 #include "device_sort_dev.hpp"
 #include "sketch_dev.hpp"
 #include "fastx_dev.hpp"     // the readers' kernels (fastx_lines_kernel, fastx_classify_kernel, fastx_copy_kernel) as well
+#include "tables.hpp"
 
 namespace mm2amd {
 
-extern const uint8_t kNt4Table[256];
 __constant__ uint8_t c_nt4_idx[256];
 
 __global__ void __launch_bounds__(256) idx_encode_kernel(const char *ascii, uint8_t *nt4, uint32_t *S, uint64_t total)

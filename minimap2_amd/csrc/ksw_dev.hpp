@@ -114,5 +114,16 @@ __host__ __device__ inline size_t ksw_dir_bytes(int qlen, int tlen, int w)
 
 // host launcher (ksw_extd2.hip); n_slots persistent waves, waves_per_block in {1,4}
 void ksw_extd2_launch(const KswLaunch &L, int n_slots, int waves_per_block, int team, void *stream /* hipStream_t */);
+void ksw_gapfill_launch(const KswLaunch &L, int n_slots, int qcap, void *stream);             // ksw_gapfill.hip
+void ksw_stream_launch(const KswLaunch &L, int n_slots, int n_sets, void *stream);            // ksw_stream.hip
+size_t ksw_stream_slot_bytes(int n_sets);
+int ksw_stream_waves(int n_sets);
+void ksw_splice_launch(const KswLaunch &L, int n_slots, int n_sets, bool self, void *stream); // ksw_splice.hip
+void ksw_ext_launch(const KswLaunch &L, int n_slots, bool right, int n_sets, void *stream);   // ksw_ext.hip
+void ksw_extq_launch(const KswLaunch &L, int n_slots, bool right, int n_sets, void *stream);  // ksw_extq.hip
+void ksw_band_launch(const KswLaunch &L, int n_slots, int n_sets, void *stream);              // ksw_band.hip
+int ksw_band_waves(int n_sets);
+int ksw_band_slots(int n_sets);
+size_t ksw_band_slot_bytes(int n_sets, int max_rows);
 
 } // namespace mm2amd

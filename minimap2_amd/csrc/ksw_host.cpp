@@ -37,18 +37,6 @@ inline int fast_waves(int tier) { return kFastQCap[tier] > 512 ? 4 : 6; } // wav
 inline int stream_sets(int tier) { return ksw_stream_sets(tier); }
 }
 
-void ksw_gapfill_launch(const KswLaunch &L, int n_slots, int qcap, void *stream); // ksw_gapfill.hip
-void ksw_stream_launch(const KswLaunch &L, int n_slots, int n_sets, void *stream);  // ksw_stream.hip
-size_t ksw_stream_slot_bytes(int n_sets);
-int ksw_stream_waves(int n_sets);
-void ksw_splice_launch(const KswLaunch &L, int n_slots, int n_sets, bool self, void *stream); // ksw_splice.hip
-void ksw_ext_launch(const KswLaunch &L, int n_slots, bool right, int n_sets, void *stream);               // ksw_ext.hip
-void ksw_extq_launch(const KswLaunch &L, int n_slots, bool right, int n_sets, void *stream);              // ksw_extq.hip
-void ksw_band_launch(const KswLaunch &L, int n_slots, int n_sets, void *stream);    // ksw_band.hip
-int ksw_band_waves(int n_sets);
-int ksw_band_slots(int n_sets);
-size_t ksw_band_slot_bytes(int n_sets, int max_rows);
-
 void KswRunner::run_jobs(const KswJob *jobs, size_t n, const uint8_t *d_qpool, const uint8_t *d_tpool, const uint32_t *d_S,
                          const KswScoring &sc, KswRes *res, const uint32_t **cigar_out, size_t *n_cigar_out, hipStream_t stream, const KswJob *d_jobs_in)
 {

@@ -19,13 +19,13 @@
 #include "sketch_dev.hpp"
 #include "sdust_dev.hpp"     // sdust_kernel (the masked regions themselves, one wavefront per read) as well
 #include "kernel_prof.hpp"
+#include "tables.hpp"
 
 namespace mm2amd {
 
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 __constant__ uint8_t c_nt4[256];
-extern const uint8_t kNt4Table[256];
 static bool g_nt4_uploaded = false;
 
 static void upload_tables(hipStream_t s)
