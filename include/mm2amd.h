@@ -225,6 +225,44 @@ int mm2amd_hits_merge_host_batch(int n_seg, const uint64_t *seg_off, const mm2am
                                  mm2amd_hm_out_t *out, mm2amd_hm_seg_t *seg, double *core_seconds);
 int mm2amd_hits_merge_limits(int *narrow_cap, int *wide_cap, int *max_hits);
 
+/* Pairing the two mates of a batch of fragments: mm_pair (pe.c:81-182) followed by mm_set_pe_thru (pe.c:50-68) -- pair_kernel, one wavefront
+ * per fragment.  Fragment f owns hits[hit0, hit0 + n[0] + n[1]): segment 0's hits, then segment 1's, as they stand after mm_set_mapq2 (id,
+ * parent, mapq, sam_pri; dp_max is mm_extra_t::dp_max: every hit is aligned).  The fragments' ranges must not overlap; out entries between
+ * them are unspecified after a call.  max_gap_ref is per fragment (the mapper's frag_gap).
+ * out[k] answers hits[k]: parent and mapq are the record's fields after the call, flags holds MM2AMD_PE_SAM_PRI (as it stands after the call),
+ * MM2AMD_PE_PROPER_FRAG (pe.c:143: the two hits of the pair) and MM2AMD_PE_THRU (pe.c:65).  A fragment with an unmapped mate (n[s] == 0) is
+ * answered unchanged (pe.c:102-105 returns before mm_set_pe_thru) by the entry point itself, as MM2AMD_PE_PATH_NARROW.
+ * res[f].n_pairs is the number of candidate pairs over the dp_max bar (sc.n, pe.c:130), best[s] the position of the pair's hit in segment s
+ * (-1: no pair, pe.c:139), status MM2AMD_PE_OK or MM2AMD_PE_BAD_PARENT -- a parent that does not index its own segment, where pe.c:146 would read
+ * out of bounds: the fragment is answered unchanged --, and path the class that ran the fragment:
+ *   MM2AMD_PE_PATH_NARROW  up to narrow_cap (64) ends, one per lane
+ *   MM2AMD_PE_PATH_WIDE    up to wide_cap (1024) ends, 36 KB of LDS
+ *   MM2AMD_PE_PATH_HOST    more ends than that, or more than 64 ends two of which have equal keys (pe.c:95; radix_sort_pair's order among them is
+ *                          then the cycle walk's, which the host replays): the same rules on the host's pool threads, inside the same call
+ * MM2AMD_EINVAL for a negative count, a null array with work to do, match_sc <= 0, a segment above max_hits, overlapping ranges or ranges that
+ * span more than 2^31 hits; n_frag == 0 returns 0; MM2AMD_ENODEV without a device.  mm2amd_pair_host_batch is the host twin (test and benchmark
+ * hook; no device): the same rules on n_threads threads, path is MM2AMD_PE_PATH_HOST throughout (an unmapped mate included); *core_seconds,
+ * unless NULL, receives the threads' summed time. */
+#define MM2AMD_PE_PATH_NARROW 0
+#define MM2AMD_PE_PATH_WIDE   1
+#define MM2AMD_PE_PATH_HOST   2
+#define MM2AMD_PE_OK 0                /* mm2amd_pe_res_t::status */
+#define MM2AMD_PE_BAD_PARENT 1
+#define MM2AMD_PE_REV 1u              /* mm2amd_pe_hit_t::flags */
+#define MM2AMD_PE_SAM_PRI 2u          /* also in mm2amd_pe_out_t::flags */
+#define MM2AMD_PE_PROPER_FRAG 4u      /* mm2amd_pe_out_t::flags */
+#define MM2AMD_PE_THRU 8u
+typedef struct { int32_t rid, rs, re, qs, qe, dp_max, id, parent, mapq; uint32_t hash, flags, reserved; } mm2amd_pe_hit_t;
+typedef struct { int32_t parent, mapq; uint32_t flags; int32_t reserved; } mm2amd_pe_out_t;
+typedef struct { uint64_t hit0; int32_t n[2], qlen[2], max_gap_ref, reserved; } mm2amd_pe_frag_t;
+typedef struct { int32_t path, status, n_pairs, best[2], reserved; } mm2amd_pe_res_t;
+typedef struct { int32_t pe_bonus, sub_diff /* 2 a + b */, match_sc /* a */, reserved; } mm2amd_pe_opt_t;
+int mm2amd_pair_batch(int n_frag, const mm2amd_pe_frag_t *frag, const mm2amd_pe_hit_t *hits, const mm2amd_pe_opt_t *opt, mm2amd_pe_out_t *out,
+                      mm2amd_pe_res_t *res);
+int mm2amd_pair_host_batch(int n_frag, const mm2amd_pe_frag_t *frag, const mm2amd_pe_hit_t *hits, const mm2amd_pe_opt_t *opt, int n_threads,
+                           mm2amd_pe_out_t *out, mm2amd_pe_res_t *res, double *core_seconds);
+int mm2amd_pair_limits(int *narrow_cap, int *wide_cap, int *max_hits);
+
 /* FASTA / FASTQ text into sequence records: kseq_read (kseq.h:192-232, with ks_getuntil2's CR rule, kseq.h:101-149) + kseq2bseq (bseq.c:65-78:
  * U -> T, u -> t; qual and comment only on request and when not empty) over a buffer in memory -- fastx_lines_kernel, fastx_classify_kernel and
  * fastx_copy_kernel for the two regular shapes, the host's parser (fastx.hpp) for everything else.  The batching of mm_bseq_read3 (bseq.c:80-119)

@@ -75,6 +75,10 @@ class HmOpt(C.Structure):  # mm2amd_hm_opt_t
                 ("sub_diff", C.c_int32), ("min_diff", C.c_int32), ("min_strand_sc", C.c_int32), ("flags", C.c_uint32)]
 
 
+class PeOpt(C.Structure):  # mm2amd_pe_opt_t
+    _fields_ = [(n, C.c_int32) for n in ("pe_bonus", "sub_diff", "match_sc", "reserved")]
+
+
 class FastxRec(C.Structure):  # mm2amd_fastx_rec_t
     _fields_ = [("name", C.c_uint64), ("comment", C.c_uint64), ("seq", C.c_uint64), ("qual", C.c_uint64), ("name_len", C.c_uint32),
                 ("comment_len", C.c_uint32), ("l_seq", C.c_int32), ("reserved", C.c_int32)]
@@ -151,6 +155,9 @@ SDUST_PATH_NARROW, SDUST_PATH_WIDE = 0, 1  # MM2AMD_SDUST_PATH_*
 HM_PATH_NARROW, HM_PATH_WIDE, HM_PATH_HOST = 0, 1, 2  # MM2AMD_HM_PATH_*
 HM_REV, HM_INV, HM_ALT, HM_ALIGNED, HM_SAM_PRI, HM_STRAND_RETAINED = 1, 2, 4, 8, 16, 32  # MM2AMD_HM_*: flags of a hit (the last two also of a result)
 HM_HARD_MLEVEL, HM_ALL_CHAINS, HM_CHECK_STRAND, HM_WAVE_PARENTS = 1, 2, 4, 8  # MM2AMD_HM_*: flags of the options
+PE_PATH_NARROW, PE_PATH_WIDE, PE_PATH_HOST = 0, 1, 2  # MM2AMD_PE_PATH_*
+PE_OK, PE_BAD_PARENT = 0, 1  # MM2AMD_PE_*: status of a fragment
+PE_REV, PE_SAM_PRI, PE_PROPER_FRAG, PE_THRU = 1, 2, 4, 8  # MM2AMD_PE_*: flags of a hit (the first two) and of a result (the last three)
 FASTX_WITH_QUAL, FASTX_WITH_COMMENT = 1, 2  # MM2AMD_FASTX_WITH_*
 FASTX_PATH_HOST, FASTX_PATH_FASTQ4, FASTX_PATH_FASTA = 0, 1, 2  # MM2AMD_FASTX_PATH_*
 F_COPY_COMMENT, F_FRAG_MODE = 0x2000000, 0x2000  # MM_F_COPY_COMMENT, MM_F_FRAG_MODE (minimap.h:35, :23)
@@ -207,6 +214,10 @@ def _bind(L):
             L.mm2amd_hits_merge_batch.argtypes = [C.c_int, vp, vp, C.POINTER(HmOpt), vp, vp]
             L.mm2amd_hits_merge_host_batch.argtypes = [C.c_int, vp, vp, C.POINTER(HmOpt), C.c_int, vp, vp, C.POINTER(C.c_double)]
             L.mm2amd_hits_merge_limits.argtypes = [ip, ip, ip]
+        if hasattr(L, "mm2amd_pair_batch"):
+            L.mm2amd_pair_batch.argtypes = [C.c_int, vp, vp, C.POINTER(PeOpt), vp, vp]
+            L.mm2amd_pair_host_batch.argtypes = [C.c_int, vp, vp, C.POINTER(PeOpt), C.c_int, vp, vp, C.POINTER(C.c_double)]
+            L.mm2amd_pair_limits.argtypes = [ip, ip, ip]
         if hasattr(L, "mm2amd_split_open"):
             L.mm2amd_split_open.restype = vp
             L.mm2amd_split_open.argtypes = [C.c_char_p, vp, C.c_int]
@@ -814,6 +825,60 @@ def hits_merge_limits():
     """mm2amd_hits_merge_limits: narrow_cap and wide_cap (hits a segment may have in either launch class), max_hits (of a segment at all)"""
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
     _check(lib().mm2amd_hits_merge_limits(C.byref(a), C.byref(b), C.byref(c)))
+    return {"narrow_cap": a.value, "wide_cap": b.value, "max_hits": c.value}
+
+
+PE_HIT_DTYPE = [(n, "<i4") for n in ("rid", "rs", "re", "qs", "qe", "dp_max", "id", "parent", "mapq")] + [("hash", "<u4"), ("flags", "<u4"), ("reserved", "<u4")]
+PE_OUT_DTYPE = [("parent", "<i4"), ("mapq", "<i4"), ("flags", "<u4"), ("reserved", "<i4")]
+PE_FRAG_DTYPE = [("hit0", "<u8"), ("n", "<i4", (2,)), ("qlen", "<i4", (2,)), ("max_gap_ref", "<i4"), ("reserved", "<i4")]  # mm2amd_pe_frag_t
+PE_RES_DTYPE = [("path", "<i4"), ("status", "<i4"), ("n_pairs", "<i4"), ("best", "<i4", (2,)), ("reserved", "<i4")]  # mm2amd_pe_res_t
+
+
+def _pe_call(call, frags, pe_bonus, sub_diff, match_sc):
+    import numpy as np
+    n = len(frags)
+    fr = np.zeros(max(n, 1), dtype=PE_FRAG_DTYPE)
+    at = 0
+    for i, (h0, h1, qlens, gap) in enumerate(frags):
+        fr[i]["hit0"], fr[i]["n"], fr[i]["qlen"], fr[i]["max_gap_ref"] = at, (len(h0), len(h1)), tuple(qlens), gap
+        at += len(h0) + len(h1)
+    hits = np.zeros(max(at, 1), dtype=PE_HIT_DTYPE)
+    for i, (h0, h1, _, _) in enumerate(frags):
+        o = int(fr[i]["hit0"])
+        hits[o:o + len(h0)] = np.asarray(h0, dtype=PE_HIT_DTYPE)
+        hits[o + len(h0):o + len(h0) + len(h1)] = np.asarray(h1, dtype=PE_HIT_DTYPE)
+    out = np.zeros(max(at, 1), dtype=PE_OUT_DTYPE)
+    res = np.zeros(max(n, 1), dtype=PE_RES_DTYPE)
+    opt = PeOpt(pe_bonus, sub_diff, match_sc, 0)
+    _check(call(n, fr.ctypes.data, hits.ctypes.data, C.byref(opt), out.ctypes.data, res.ctypes.data))
+    outs = []
+    for i in range(n):
+        o, n0, n1 = int(fr[i]["hit0"]), int(fr[i]["n"][0]), int(fr[i]["n"][1])
+        outs.append((out[o:o + n0].copy(), out[o + n0:o + n0 + n1].copy()))
+    return outs, res[:n].copy()
+
+
+def pair_batch(frags, pe_bonus=33, sub_diff=8, match_sc=2):
+    """mm2amd_pair_batch: mm_pair and mm_set_pe_thru (pe.c:50-68, :81-182) on pair_kernel, one wavefront per fragment.  frags is a list of
+    (hits of segment 0, hits of segment 1, (qlen0, qlen1), max_gap_ref), the hits structured arrays of PE_HIT_DTYPE as they stand after
+    mm_set_mapq2; the defaults are minimap2's (a = 2, b = 4: sub_diff = 2 a + b, match_sc = a).  Returns (out, res): per fragment a pair of
+    PE_OUT_DTYPE arrays answering its hits one by one, and a PE_RES_DTYPE array (path: PE_PATH_*, status: PE_OK / PE_BAD_PARENT, n_pairs, best)."""
+    L = lib()
+    return _pe_call(lambda n, fr, hits, o, out, res: L.mm2amd_pair_batch(n, fr, hits, o, out, res), frags, pe_bonus, sub_diff, match_sc)
+
+
+def pair_host_batch(frags, pe_bonus=33, sub_diff=8, match_sc=2, n_threads=1):
+    """mm2amd_pair_host_batch: the same rules on n_threads host threads (path is PE_PATH_HOST throughout).  Returns (out, res, core_seconds)."""
+    L = lib()
+    cs = C.c_double(0)
+    r = _pe_call(lambda n, fr, hits, o, out, res: L.mm2amd_pair_host_batch(n, fr, hits, o, n_threads, out, res, C.byref(cs)), frags, pe_bonus, sub_diff, match_sc)
+    return r + (cs.value,)
+
+
+def pair_limits():
+    """mm2amd_pair_limits: narrow_cap and wide_cap (ends -- hits of both segments -- a fragment may have in either launch class), max_hits (of a segment at all)"""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().mm2amd_pair_limits(C.byref(a), C.byref(b), C.byref(c)))
     return {"narrow_cap": a.value, "wide_cap": b.value, "max_hits": c.value}
 
 

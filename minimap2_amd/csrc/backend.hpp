@@ -12,6 +12,7 @@
 #include "region_dev.hpp"
 #include "rec_text.hpp"
 #include "junc_text.hpp"
+#include "../../include/mm2amd.h"
 
 namespace mm2amd {
 
@@ -128,6 +129,14 @@ public:
 	virtual const char *rec_text_write(uint64_t /*total*/) { return nullptr; }
 	virtual const RecRes *junc_text_size(int64_t /*flag*/) { return nullptr; }
 	virtual const char *junc_text_write(uint64_t /*total*/) { return nullptr; }
+	// mm_pair and mm_set_pe_thru for a sub-batch's two-segment fragments on the device (pair.hpp), for the mapper's finish step with MM2AMD_DEVICE_PAIR=1.
+	//   pair_begin   the lane's pinned tables for n_frag fragments and n_hits hits, for the caller to fill (mm2amd.h: mm2amd_pair_batch's layout);
+	//                false: not here -- the caller pairs on the host;
+	//   pair_run     uploads them, runs pair_kernel's launch classes on the lane's stream (no other lane waits), answers the host class on up to
+	//                n_threads threads; out and res of pair_begin then hold every answer.
+	struct PairTables { mm2amd_pe_frag_t *frag = nullptr; mm2amd_pe_hit_t *hits = nullptr; mm2amd_pe_out_t *out = nullptr; mm2amd_pe_res_t *res = nullptr; };
+	virtual bool pair_begin(int /*lane*/, size_t /*n_frag*/, size_t /*n_hits*/, PairTables & /*t*/) { return false; }
+	virtual void pair_run(int /*lane*/, size_t /*n_frag*/, const mm2amd_pe_opt_t & /*opt*/, int /*n_threads*/) {}
 	virtual bool finishes_regions() const { return false; }
 	virtual void finish_regions(int /*lane*/, const std::vector<FinRegion> & /*regions*/, const std::vector<FinPiece> & /*pieces*/, size_t /*out_words*/, const int8_t * /*mat25*/,
 	                            int /*q*/, int /*e*/, bool /*log_gap*/, std::vector<FinResult> & /*results*/, const uint32_t ** /*cigars*/, EqxOut * /*eqx*/ = nullptr) {}

@@ -962,6 +962,21 @@ public:
 		prof.collect();
 	}
 
+	// ---- mm_pair on the device (pair.hpp) for the lane's sub-batch: the lane's stream and buffers, the lane's profiler slot
+	bool pair_begin(int lane_id, size_t n_frag, size_t n_hits, PairTables &t) override
+	{
+		HIP_CHECK(hipSetDevice(dev_));
+		Lane &ln = *lanes_.at(lane_id);
+		t.frag = ln.h_pe_frag.ensure(n_frag + 1), t.hits = ln.h_pe_hits.ensure(n_hits + 1), t.out = ln.h_pe_out.ensure(n_hits + 1), t.res = ln.h_pe_res.ensure(n_frag + 1);
+		return true;
+	}
+	void pair_run(int lane_id, size_t n_frag, const mm2amd_pe_opt_t &opt, int n_threads) override
+	{
+		HIP_CHECK(hipSetDevice(dev_));
+		Lane &ln = *lanes_.at(lane_id);
+		mm2amd::pair_run(ln.pair, (int)n_frag, ln.h_pe_frag.p, ln.h_pe_hits.p, opt, ln.h_pe_out.p, ln.h_pe_res.p, n_threads, kernel_profiler(lane_id, replica_), ln.stream, stream_wait);
+	}
+
 	// ---- the output stage on the device (rec_text.hpp).  Its stream, buffers and profiler slot are its own; of the backend it reads the device's ordinal, the
 	// packed sequence's address and the index's name table, none of which changes after construction -- so it runs beside the lanes' mapping.
 	bool writes_records() const override { return true; }

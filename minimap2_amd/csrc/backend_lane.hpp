@@ -108,6 +108,10 @@ struct Lane {
 	PinBuf<FinRegion> h_fin_regions; PinBuf<FinPiece> h_fin_pieces; PinBuf<uint32_t> h_fin_out; PinBuf<FinResult> h_fin_res;
 	EqxBufs eqx_fin;
 
+	// ---- pair_begin / pair_run (pair.hpp): the caller's tables in pinned memory, the launch's buffers
+	PairBufs pair;
+	PinBuf<mm2amd_pe_frag_t> h_pe_frag; PinBuf<mm2amd_pe_hit_t> h_pe_hits; PinBuf<mm2amd_pe_out_t> h_pe_out; PinBuf<mm2amd_pe_res_t> h_pe_res;
+
 	// ---- align_regions (region_dev.hpp): the lane's last seed_chain() in device terms, the hit / window / piece arrays, the results' host copies
 	long rg_lo = 0; size_t rg_n = 0; uint64_t rg_n_v = 0, rg_n_v2 = 0, rg_n_u = 0, rg_n_u2 = 0;
 	bool rg_lazy = false;

@@ -1,5 +1,6 @@
 // C ABI of libmm2amd.so (declared in include/mm2amd.h): the kernel-level entry points.
 #include <map>
+#include <algorithm>
 #include <cstring>
 #include "capi_internal.hpp"
 #include "device_ctx.hpp"
@@ -82,6 +83,40 @@ int hm_check_args(const char *who, int n_seg, const uint64_t *seg_off, const mm2
 		if (seg_off[s + 1] < seg_off[s] || seg_off[s + 1] - seg_off[s] > (uint64_t)kHmMaxHits)
 			return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad offsets (descending, or a segment above the hit limit)");
 	if (n_seg > 0 && seg_off[n_seg] > seg_off[0] && (!hits || !out)) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": hits without arrays");
+	return 0;
+}
+
+struct PairApiState { PairBufs bufs; }; // mm2amd_pair_batch: kept between calls
+PairApiState &pe_state() { static PairApiState s; return s; }
+
+int pe_check_args(const char *who, int n_frag, const mm2amd_pe_frag_t *frag, const mm2amd_pe_hit_t *hits, const mm2amd_pe_opt_t *opt, const mm2amd_pe_out_t *out,
+                  const mm2amd_pe_res_t *res, std::vector<uint32_t> &order)
+{
+	if (n_frag < 0 || (n_frag > 0 && (!frag || !opt || !res))) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad arguments");
+	if (n_frag > 0 && opt->match_sc <= 0) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": match_sc must be positive");
+	bool ascending = true;
+	uint64_t end = 0, lo = ~(uint64_t)0, hi = 0;
+	for (int f = 0; f < n_frag; ++f) {
+		const mm2amd_pe_frag_t &F = frag[f];
+		if (F.n[0] < 0 || F.n[1] < 0 || F.n[0] > kPeMaxHits || F.n[1] > kPeMaxHits || F.hit0 > (uint64_t)1 << 48)
+			return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": bad fragment (a negative count, or a segment above the hit limit)");
+		const uint64_t m = (uint64_t)F.n[0] + (uint64_t)F.n[1];
+		if (m == 0) continue;
+		ascending = ascending && F.hit0 >= end;
+		end = F.hit0 + m, lo = std::min(lo, F.hit0), hi = std::max(hi, end);
+	}
+	if (hi == 0) return 0;
+	if (!hits || !out) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": hits without arrays");
+	if (hi - lo > (uint64_t)1 << 31) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": the fragments span more than 2^31 hits");
+	if (!ascending) { // (the usual batch lists its fragments in the order of their hits: one pass above; otherwise by start)
+		order.clear();
+		for (int f = 0; f < n_frag; ++f) if (frag[f].n[0] + frag[f].n[1] > 0) order.push_back((uint32_t)f);
+		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return frag[a].hit0 < frag[b].hit0; });
+		for (size_t k = 1; k < order.size(); ++k) {
+			const mm2amd_pe_frag_t &A = frag[order[k - 1]];
+			if (A.hit0 + (uint64_t)A.n[0] + (uint64_t)A.n[1] > frag[order[k]].hit0) return capi_fail(MM2AMD_EINVAL, std::string("[mm2amd] ") + who + ": the fragments' hit ranges overlap");
+		}
+	}
 	return 0;
 }
 
@@ -724,6 +759,46 @@ int mm2amd_hits_merge_host_batch(int n_seg, const uint64_t *seg_off, const mm2am
 	});
 }
 
+int mm2amd_pair_limits(int *narrow_cap, int *wide_cap, int *max_hits)
+{
+	if (narrow_cap) *narrow_cap = kPeNarrowCap;
+	if (wide_cap) *wide_cap = kPeWideCap;
+	if (max_hits) *max_hits = kPeMaxHits;
+	return 0;
+}
+
+int mm2amd_pair_batch(int n_frag, const mm2amd_pe_frag_t *frag, const mm2amd_pe_hit_t *hits, const mm2amd_pe_opt_t *opt, mm2amd_pe_out_t *out,
+                      mm2amd_pe_res_t *res)
+{
+	std::vector<uint32_t> order;
+	if (const int rc = pe_check_args("pair_batch", n_frag, frag, hits, opt, out, res, order)) return rc;
+	if (n_frag == 0) return 0;
+	return guarded([&]() -> int {
+		DeviceScope dev; DeviceCtx &dc = dev.dc;
+		pair_run(pe_state().bufs, n_frag, frag, hits, *opt, out, res, effective_cpus(), kernel_profiler(0), dc.stream, stream_sync);
+		return 0;
+	});
+}
+
+int mm2amd_pair_host_batch(int n_frag, const mm2amd_pe_frag_t *frag, const mm2amd_pe_hit_t *hits, const mm2amd_pe_opt_t *opt, int n_threads,
+                           mm2amd_pe_out_t *out, mm2amd_pe_res_t *res, double *core_seconds)
+{
+	std::vector<uint32_t> order;
+	if (const int rc = pe_check_args("pair_host_batch", n_frag, frag, hits, opt, out, res, order)) return rc;
+	if (core_seconds) *core_seconds = 0;
+	if (n_frag == 0) return 0;
+	return guarded([&]() -> int {
+		std::vector<double> busy((size_t)std::max(n_threads, 1), 0.0);
+		parallel_for(n_threads, (long)n_frag, [&](long f, int tid) {
+			const double t0 = Trace::now();
+			pe_host_fragment(frag[f], hits + frag[f].hit0, *opt, out + frag[f].hit0, res + f, MM2AMD_PE_PATH_HOST);
+			busy[tid] += Trace::now() - t0;
+		}, 64);
+		if (core_seconds) for (double b : busy) *core_seconds += b;
+		return 0;
+	});
+}
+
 void *mm2amd_split_open(const char *prefix, const mm2amd_index_t *idx, int part_no)
 {
 	void *h = nullptr;
@@ -761,6 +836,7 @@ void *mm2amd_split_merge_open(const char *prefix, int n_parts, const void *opt)
 	guarded([&]() -> int {
 		SplitMerger *m = split_merge_open(prefix, n_parts, *(const ref::MapOpt *)opt);
 		m->device = split_device_route();
+		m->device_pair = pair_device_env();
 		h = m;
 		return 0;
 	});

@@ -10,6 +10,7 @@
 #include "host_prof.hpp"
 #include "chain_dump.hpp"
 #include "chain_host.hpp"
+#include "pair.hpp"
 #include "threads.hpp"
 #include "trace.hpp"
 #include <atomic>
@@ -82,6 +83,7 @@ Mapper::Mapper(const FlatIndex &fi, const MapOpt &opt, Backend &be, int n_thread
 		gen_score_matrix(opt, O.mat);
 		rgn_ok_ = region_path_supported(opt, fi.flag, fi.n_alt, fi.has_junc || fi.has_jump || fi.has_spsc);
 	}
+	device_pair_ = pair_device_env();
 	// MM_F_INDEPEND_SEG / MM_F_WEAK_PAIRING are resolved at the boundary (capi_map.cpp)
 	if (opt.flag & F_QSTRAND) { // reverse-strand hits in query-strand coordinates: DP targets are composed (reverse-complemented) into the byte pool
 		if (!be.supports_byte_targets()) throw std::invalid_argument("[mm2amd] --qstrand needs a backend with composed DP targets");
@@ -728,6 +730,14 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 
 		// ---- final hit selection and MAPQ (map.c:215-225, :339-342), pairing (map.c:353-354) ----
 		t0 = now(), c0 = cpu_now(), d0 = thr_now();
+		const auto pair_hits_of = [&](ReadResult &res, const ReadView &rv) { // map.c:353-354 on the host
+			const int qlens[2] = { rv.len, rv.len2 };
+			RegVec both[2];
+			both[0].swap(res.regs), both[1].swap(res.regs2);
+			pair_hits(res.frag_gap, opt_.pe_bonus, opt_.a * 2 + opt_.b, opt_.a, qlens, both);
+			both[0].swap(res.regs), both[1].swap(res.regs2);
+		};
+		if (device_pair_) ds.pe_n.assign((size_t)m, 0), ds.pe_frag.resize((size_t)m), ds.pe_hit0.resize((size_t)m);
 		parallel_for(n_threads_, m, [&](long i, int tid) {
 			ReadResult &res = out[live_id[lo + i]];
 			const ReadView &rv = live[lo + i];
@@ -746,13 +756,46 @@ void Mapper::process_sub(BatchRun &batch, long lo, long hi, int lane, std::vecto
 			if (fi_.has_jump && n_segs == 1 && (opt_.flag & F_SPLICE)) // map.c:362-364: clipped ends hop over annotated junctions
 				for (Reg &r : res.regs) jump_split(fi_, opt_, rv.len, rv.seq, r, 0);
 			if (n_segs == 2 && opt_.pe_ori >= 0) {
-				const int qlens[2] = { rv.len, rv.len2 };
-				RegVec both[2];
-				both[0].swap(res.regs), both[1].swap(res.regs2);
-				pair_hits(res.frag_gap, opt_.pe_bonus, opt_.a * 2 + opt_.b, opt_.a, qlens, both);
-				both[0].swap(res.regs), both[1].swap(res.regs2);
+				if (device_pair_) { // pairing waits for the whole sub-batch (below); a fragment with an unmapped mate stays as it is (pe.c:102-105)
+					bool flat = !res.regs.empty() && !res.regs2.empty();
+					for (const Reg &r : res.regs) flat = flat && r.p;
+					for (const Reg &r : res.regs2) flat = flat && r.p;
+					ds.pe_n[i] = flat ? (uint32_t)(res.regs.size() + res.regs2.size()) : 0;
+					if (flat || res.regs.empty() || res.regs2.empty()) return;
+				}
+				pair_hits_of(res, rv);
 			}
 		});
+		if (device_pair_ && opt_.pe_ori >= 0) { // mm_pair on the device: the sub-batch's two-segment fragments flattened, one call on the lane's stream, the answers put back
+			size_t n_frag = 0;
+			uint64_t n_hits = 0;
+			for (long i = 0; i < m; ++i) { ds.pe_frag[i] = (uint32_t)n_frag, ds.pe_hit0[i] = n_hits; if (ds.pe_n[i]) ++n_frag, n_hits += ds.pe_n[i]; }
+			Backend::PairTables T;
+			if (n_frag > 0 && !be_.pair_begin(lane, n_frag, (size_t)n_hits, T)) { // not here: the host's routine
+				parallel_for(n_threads_, m, [&](long i, int) { if (ds.pe_n[i]) pair_hits_of(out[live_id[lo + i]], live[lo + i]); });
+			} else if (n_frag > 0) {
+				parallel_for(n_threads_, m, [&](long i, int) {
+					if (!ds.pe_n[i]) return;
+					const ReadResult &res = out[live_id[lo + i]];
+					const ReadView &rv = live[lo + i];
+					mm2amd_pe_frag_t &F = T.frag[ds.pe_frag[i]];
+					F.hit0 = ds.pe_hit0[i], F.n[0] = (int32_t)res.regs.size(), F.n[1] = (int32_t)res.regs2.size(), F.qlen[0] = rv.len, F.qlen[1] = rv.len2, F.max_gap_ref = res.frag_gap, F.reserved = 0;
+					mm2amd_pe_hit_t *h = T.hits + ds.pe_hit0[i];
+					for (const Reg &r : res.regs) pe_flat_hit(*h++, r);
+					for (const Reg &r : res.regs2) pe_flat_hit(*h++, r);
+				}, 256);
+				const mm2amd_pe_opt_t po = { opt_.pe_bonus, opt_.a * 2 + opt_.b, opt_.a, 0 };
+				be_.pair_run(lane, n_frag, po, n_threads_);
+				for (size_t f = 0; f < n_frag; ++f) if (T.res[f].status != MM2AMD_PE_OK) throw std::runtime_error("[mm2amd] pairing: a hit's parent does not index its segment");
+				parallel_for(n_threads_, m, [&](long i, int) {
+					if (!ds.pe_n[i]) return;
+					ReadResult &res = out[live_id[lo + i]];
+					const mm2amd_pe_out_t *o = T.out + ds.pe_hit0[i];
+					for (Reg &r : res.regs) pe_apply(r, *o++);
+					for (Reg &r : res.regs2) pe_apply(r, *o++);
+				}, 256);
+			}
+		}
 		Trace::get().add(lane, "host:finish", t0, now());
 		stats.t_finish += now() - t0;
 		stats.c_finish += cpu_now() - c0; stats.d_finish += thr_now() - d0; d0 = thr_now();

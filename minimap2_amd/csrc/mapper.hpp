@@ -80,6 +80,9 @@ private:
 		std::vector<size_t> fin_base;
 		std::vector<Backend::RegionReadIn> rg_in;   // Backend::align_regions: per read the hash of map.c:246-248 and whether the host keeps it
 		std::vector<uint8_t> on_dev;                // per read: finished by the device path
+		std::vector<uint32_t> pe_n;                 // MM2AMD_DEVICE_PAIR: per read the hits Backend::pair_run is given (0: none), its fragment's number and first hit
+		std::vector<uint32_t> pe_frag;
+		std::vector<uint64_t> pe_hit0;
 	};
 	std::vector<std::unique_ptr<DriverScratch>> scratch_;
 	// One batch on its way through the lanes: its resident set (ours and the backend's), its sub-batches and who has taken them, its results.
@@ -111,6 +114,7 @@ private:
 	Backend &be_;
 	int n_threads_;
 	RgnOpts rgn_opts_{};
+	bool device_pair_ = false; // MM2AMD_DEVICE_PAIR=1 when the mapper was made: mm_pair through Backend::pair_run (pair.hpp)
 	bool rgn_ok_ = false; // the options and the index allow Backend::align_regions (region_path_supported)
 	struct Staged { long n = 0; std::vector<ReadView> live; std::vector<long> live_id; std::vector<uint64_t> qoff; };
 	Staged sets_[2];

@@ -27,6 +27,7 @@
 #include "junc_text_dev.hpp" // and junc_text_kernel (--write-junc: the splice junctions of a hit)
 #include "cigar_eqx_dev.hpp" // and cigar_eqx_kernel (MM_F_EQX: the finished CIGAR's matches cut into = and X)
 #include "hits_merge_dev.hpp" // and hits_merge_kernel (a split-index merge's hit-list rules)
+#include "pair_dev.hpp"       // and pair_kernel (mm_pair and mm_set_pe_thru for a batch of fragments)
 
 namespace mm2amd {
 

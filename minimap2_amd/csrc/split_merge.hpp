@@ -4,7 +4,7 @@
 //            frag_gap and per hit the raw mm_reg1_t (its p field zeroed), with MM_F_CIGAR followed by capacity and the mm_extra_t block.
 //   merger   opens the parts, keeps their names and lengths as an index without sequence or minimizers, and per mini-batch reads every
 //            segment's records from all parts, shifts rid, and applies merge_hits' steps.  mm_update_dp_max before and mm_set_mapq2 / mm_pair after
-//            are the host's (hits.cpp); the rules between them go to hits_merge_kernel or, with MM2AMD_DEVICE_MERGE=0 -- and by default, see the
+//            are the host's (hits.cpp; with MM2AMD_DEVICE_PAIR=1 mm_pair goes to pair_kernel); the rules between them go to hits_merge_kernel or, with MM2AMD_DEVICE_MERGE=0 -- and by default, see the
 //            measurement in DESIGN.md -- to hits.cpp's own routines.
 #pragma once
 #include <cerrno>
@@ -19,6 +19,7 @@
 #include "format.hpp"
 #include "hits.hpp"
 #include "hits_merge.hpp"
+#include "pair.hpp"
 
 namespace mm2amd {
 
@@ -78,6 +79,7 @@ struct SplitMerger {
 	ref::MapOpt opt;
 	mm2amd_hm_opt_t hm;
 	bool device = false;
+	bool device_pair = false; // MM2AMD_DEVICE_PAIR=1: mm_pair through mm2amd_pair_batch, one call per mini-batch
 	void get(int j, void *p, size_t n) { if (n && fread(p, 1, n, fp[(size_t)j]) != n) throw std::runtime_error("[mm2amd] split: " + split_tmp_name(prefix, j) + " ends early"); }
 	~SplitMerger() { for (FILE *f : fp) if (f) fclose(f); }
 };
@@ -218,9 +220,37 @@ inline void split_merge_batch(SplitMerger &m, int n_frag, const int *seg_off, co
 			const int st = seg_off ? seg_off[f] : f, ns = n_seg ? n_seg[f] : 1;
 			for (int k = st; k < st + ns; ++k)
 				set_mapq(all[(size_t)k], opt.min_chain_score, opt.a, rep_len[k], (opt.flag & (ref::F_SR | ref::F_SR_RNA)) != 0, (opt.flag & ref::F_SPLICE) != 0);
-			if (ns == 2 && opt.pe_ori >= 0 && cigar) {
+			if (ns == 2 && opt.pe_ori >= 0 && cigar && !m.device_pair) {
 				const int qlens[2] = { seq[st].l_seq, seq[st + 1].l_seq };
 				pair_hits(frag_gap[st + 1], opt.pe_bonus, opt.a * 2 + opt.b, opt.a, qlens, &all[(size_t)st]);
+			}
+		}
+		if (m.device_pair && opt.pe_ori >= 0 && cigar) { // mm_pair on pair_kernel: the mini-batch's two-segment fragments flattened, one call, the answers put back
+			std::vector<mm2amd_pe_frag_t> fr;
+			std::vector<int> first_seg;
+			uint64_t n_hits = 0;
+			for (int f = 0; f < n_frag; ++f) {
+				const int st = seg_off ? seg_off[f] : f, ns = n_seg ? n_seg[f] : 1;
+				if (ns != 2) continue;
+				mm2amd_pe_frag_t F;
+				F.hit0 = n_hits, F.n[0] = (int32_t)all[(size_t)st].size(), F.n[1] = (int32_t)all[(size_t)st + 1].size();
+				F.qlen[0] = seq[st].l_seq, F.qlen[1] = seq[st + 1].l_seq, F.max_gap_ref = frag_gap[st + 1], F.reserved = 0;
+				n_hits += (uint64_t)F.n[0] + (uint64_t)F.n[1];
+				fr.push_back(F), first_seg.push_back(st);
+			}
+			std::vector<mm2amd_pe_hit_t> hits((size_t)n_hits + 1);
+			std::vector<mm2amd_pe_out_t> out(hits.size());
+			std::vector<mm2amd_pe_res_t> res(fr.size() + 1);
+			for (size_t k = 0; k < fr.size(); ++k) {
+				size_t at = (size_t)fr[k].hit0;
+				for (int s = 0; s < 2; ++s) for (const Reg &r : all[(size_t)first_seg[k] + s]) pe_flat_hit(hits[at++], r);
+			}
+			const mm2amd_pe_opt_t po = { opt.pe_bonus, opt.a * 2 + opt.b, opt.a, 0 };
+			if (!fr.empty() && mm2amd_pair_batch((int)fr.size(), fr.data(), hits.data(), &po, out.data(), res.data()) != 0) throw std::runtime_error(mm2amd_last_error());
+			for (size_t k = 0; k < fr.size(); ++k) {
+				if (res[k].status != MM2AMD_PE_OK) throw std::runtime_error("[mm2amd] split: a hit's parent does not index its segment");
+				size_t at = (size_t)fr[k].hit0;
+				for (int s = 0; s < 2; ++s) for (Reg &r : all[(size_t)first_seg[k] + s]) pe_apply(r, out[at++]);
 			}
 		}
 		for (int k = 0; k < n_total; ++k) {

@@ -9,6 +9,8 @@
 #include "region_finish.hpp"
 #include "cigar_eqx.hpp"
 #include "sdust.hpp"
+#include "pair.hpp"
+#include "threads.hpp"
 
 namespace mm2amd {
 
@@ -109,6 +111,94 @@ inline void sdust_run_class(SdustParams &P, int wide, int grid, KernelProfiler &
 	prof.begin(st);
 	sdust_launch(P, grid, st);
 	prof.end(st, wide ? "sdust_kernel[wide]" : "sdust_kernel[narrow]", 0.0, units);
+}
+
+// ---- pair_kernel (pair.hpp): the fragments by class, one launch per class, the host class and the unmapped mates answered here.  hits, out, frag
+// and res are the caller's (any host memory; a lane passes pinned buffers); arguments are checked by the caller.
+struct PairBufs {
+	DevBuf<mm2amd_pe_hit_t> d_hits; DevBuf<mm2amd_pe_out_t> d_out; DevBuf<mm2amd_pe_frag_t> d_frag; DevBuf<mm2amd_pe_res_t> d_res;
+	DevBuf<uint32_t> d_list; PinBuf<uint32_t> h_list;
+	DevBuf<float> d_logf; PinBuf<float> h_logf; bool logf_ready = false; // logf(1) .. logf(kPeLogTable) from the host's libm, filled when first needed
+	std::vector<uint32_t> host_list;
+};
+// the hits the fragments span: [*first, *last)
+inline void pair_span(int n_frag, const mm2amd_pe_frag_t *frag, uint64_t *first, uint64_t *last)
+{
+	uint64_t lo = ~(uint64_t)0, hi = 0;
+	for (int f = 0; f < n_frag; ++f) {
+		const uint64_t m = (uint64_t)frag[f].n[0] + (uint64_t)frag[f].n[1];
+		if (m == 0) continue;
+		lo = std::min(lo, frag[f].hit0), hi = std::max(hi, frag[f].hit0 + m);
+	}
+	*first = hi ? lo : 0, *last = hi;
+}
+inline void pair_run(PairBufs &B, int n_frag, const mm2amd_pe_frag_t *frag, const mm2amd_pe_hit_t *hits, const mm2amd_pe_opt_t &opt, mm2amd_pe_out_t *out, mm2amd_pe_res_t *res,
+                     int n_threads, KernelProfiler &prof, hipStream_t st, StreamWait wait)
+{
+	const size_t n = (size_t)n_frag;
+	if (n == 0) return;
+	uint64_t first = 0, last = 0;
+	pair_span(n_frag, frag, &first, &last);
+	const uint64_t total = last - first;
+	// the fragments by class: narrow ones from the front of the list, wide ones from its end; an unmapped mate is answered below, the rest is the host's
+	uint32_t *const h_list = B.h_list.ensure(n);
+	size_t n_narrow = 0, n_wide = 0;
+	double narrow_ends = 0, wide_ends = 0;
+	for (size_t f = 0; f < n; ++f) {
+		const uint64_t m = (uint64_t)frag[f].n[0] + (uint64_t)frag[f].n[1];
+		pe_res_none(res[f], MM2AMD_PE_PATH_HOST, MM2AMD_PE_OK);
+		if (frag[f].n[0] == 0 || frag[f].n[1] == 0) res[f].path = MM2AMD_PE_PATH_NARROW;
+		else if (m <= (uint64_t)kPeNarrowCap) h_list[n_narrow++] = (uint32_t)f, narrow_ends += (double)m;
+		else if (m <= (uint64_t)kPeWideCap) h_list[n - 1 - n_wide++] = (uint32_t)f, wide_ends += (double)m;
+	}
+	if (n_narrow + n_wide > 0) {
+		if (!B.logf_ready) {
+			float *t = B.h_logf.ensure((size_t)kPeLogTable + 1, 1.0);
+			t[0] = 0.0f;
+			for (int k = 1; k <= kPeLogTable; ++k) t[k] = logf((float)k);
+			B.d_logf.ensure((size_t)kPeLogTable + 1, 1.0);
+			HIP_CHECK(hipMemcpyAsync(B.d_logf.p, t, ((size_t)kPeLogTable + 1) * sizeof(float), hipMemcpyHostToDevice, st));
+			B.logf_ready = true;
+		}
+		B.d_hits.ensure(total + 1), B.d_out.ensure(total + 1), B.d_frag.ensure(n), B.d_res.ensure(n), B.d_list.ensure(n);
+		prof.begin(st); // (the copies have rows of their own in the profile: the call is bound by them)
+		HIP_CHECK(hipMemcpyAsync(B.d_hits.p, hits + first, total * sizeof(mm2amd_pe_hit_t), hipMemcpyHostToDevice, st));
+		HIP_CHECK(hipMemcpyAsync(B.d_frag.p, frag, n * sizeof(mm2amd_pe_frag_t), hipMemcpyHostToDevice, st));
+		HIP_CHECK(hipMemcpyAsync(B.d_list.p, h_list, n * 4, hipMemcpyHostToDevice, st));
+		HIP_CHECK(hipMemcpyAsync(B.d_res.p, res, n * sizeof(mm2amd_pe_res_t), hipMemcpyHostToDevice, st));
+		prof.end(st, "pair_copy[up]", (double)total * sizeof(mm2amd_pe_hit_t) + (double)n * (sizeof(mm2amd_pe_frag_t) + 4 + sizeof(mm2amd_pe_res_t)));
+		PairParams P;
+		P.hits = B.d_hits.p, P.first = first, P.frag = B.d_frag.p, P.out = B.d_out.p, P.res = B.d_res.p, P.opt = opt, P.logf_tab = B.d_logf.p;
+		if (n_narrow) {
+			P.list = B.d_list.p, P.n_list = (int)n_narrow, P.cap = kPeNarrowCap, P.path = MM2AMD_PE_PATH_NARROW;
+			prof.begin(st);
+			pair_launch(P, st);
+			prof.end(st, "pair_kernel[narrow]", 0.0, narrow_ends);
+		}
+		if (n_wide) {
+			P.list = B.d_list.p + (n - n_wide), P.n_list = (int)n_wide, P.cap = kPeWideCap, P.path = MM2AMD_PE_PATH_WIDE;
+			prof.begin(st);
+			pair_launch(P, st);
+			prof.end(st, "pair_kernel[wide]", 0.0, wide_ends);
+		}
+		prof.begin(st);
+		HIP_CHECK(hipMemcpyAsync(res, B.d_res.p, n * sizeof(mm2amd_pe_res_t), hipMemcpyDeviceToHost, st));
+		HIP_CHECK(hipMemcpyAsync(out + first, B.d_out.p, total * sizeof(mm2amd_pe_out_t), hipMemcpyDeviceToHost, st));
+		prof.end(st, "pair_copy[down]", (double)total * sizeof(mm2amd_pe_out_t) + (double)n * sizeof(mm2amd_pe_res_t));
+		wait(st);
+		prof.collect();
+	}
+	// what no launch answered: an unmapped mate (nothing changes), and the host class -- by size, or because the kernel met equal keys among more
+	// than 64 ends
+	B.host_list.clear();
+	for (size_t f = 0; f < n; ++f) {
+		if (frag[f].n[0] == 0 || frag[f].n[1] == 0 || res[f].path == MM2AMD_PE_PATH_HOST) B.host_list.push_back((uint32_t)f);
+		else if (res[f].best[0] >= frag[f].n[0] || res[f].best[1] >= frag[f].n[1]) throw HipError("[mm2amd] pair_kernel: a pair outside its fragment");
+	}
+	parallel_for(n_threads, (long)B.host_list.size(), [&](long k, int) {
+		const uint32_t f = B.host_list[(size_t)k];
+		pe_host_fragment(frag[f], hits + frag[f].hit0, opt, out + frag[f].hit0, res + f, res[f].path);
+	}, 64);
 }
 
 } // namespace mm2amd
